@@ -6,6 +6,12 @@ A "step" = one pass of the hot path over one batch per GPU: forward -> BPR loss 
 hand-written backward -> gradient all-reduce (N>1) -> dense Adam over all parameters, inputs resident
 in HBM.  Prints ONE JSON line (rank 0).  `python bench.py --gpus N --steps K --warmup W`; for N>1 launch
 with torch.distributed.run (one rank per GPU, RCCL).
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, print the line (`value`,
+`ms_per_step`, the configuration).  `--full` adds everything else the line can carry: the spread blocks, evaluation
+throughput, the data-parallel exchange timing, the per-kernel profile and rooflines, the feed throughput, the bf16-mode
+line, the other workloads and the CPU baseline (each still switched off by its --no_* option).  `--dump-outputs DIR`
+writes what the timed path computed in its last step (dump_outputs).
 """
 import argparse
 import json
@@ -292,6 +298,32 @@ def short_line(workload, B, over, steps, warmup, dev):
     return out
 
 
+def dump_outputs(d, model, losses, rows=16384):
+    """--dump-outputs DIR: what the timed path computed in its last timed step, as .npy files a caller of the path would
+    receive -- the step's three losses (loss.npy, ensemble_loss.npy, intent_loss.npy, float64) and every parameter as the
+    step's Adam update left it (param.<name>.npy, float32).  A parameter of more than 2**20 elements (the id tables) is
+    sampled: the same `rows` rows (sorted, drawn from a fixed seed) in every run.  The inputs are seeded, so two builds run
+    with the same arguments can be compared file for file.  At most 64 MB in all."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    arrays = {}
+    if losses is not None:
+        for name, t in zip(('loss', 'ensemble_loss', 'intent_loss'), losses):
+            arrays[name] = t.detach().double().cpu().numpy().reshape(1)
+    for name, p in model.named_parameters():
+        t = p.detach()
+        if t.numel() > (1 << 20):
+            idx = np.sort(np.random.default_rng(0).choice(t.shape[0], size=min(rows, t.shape[0]), replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        arrays['param.' + name] = t.float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > (64 << 20):
+        raise SystemExit('bench.py: --dump-outputs would write %.1f MB (limit 64 MB)' % (total / 2 ** 20))
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + '.npy'), a)
+
+
 def self_launch(n, argv):
     """Start the N ranks of `bench.py --gpus N` as children (python -m torch.distributed.run, one process per GPU, rendezvous on 127.0.0.1), relay
     rank 0's JSON line and check that it really is an N-rank line.  Returns the exit code."""
@@ -352,6 +384,11 @@ def main():
     ap.add_argument('--cpu_budget', type=float, default=24.0)
     ap.add_argument('--shapes', action='store_true', help='also report per-GEMM-shape timings')
     ap.add_argument('--encoder', type=str, default='', help='override the sequence encoder: BERT4Rec | GRU4Rec')
+    ap.add_argument('--full', action='store_true', help='also measure everything beyond the headline (spread blocks, evaluation, exchange, per-kernel '
+                    'profile and rooflines, feed, bf16-mode line, other workloads, CPU baseline); the --no_* options and --eval_steps, '
+                    '--spread_blocks, --shapes, --cpu_budget act on these')
+    ap.add_argument('--dump-outputs', dest='dump_outputs', metavar='DIR', default='', help='write what the timed path computed in its last '
+                    'step to DIR/<name>.npy (dump_outputs)')
     ap.add_argument('--dry_launch', action='store_true', help='stop after the process group is up: rank 0 prints {"dry_launch": true, "n_gpus": N, '
                     '"rccl_ranks": N, "backend": ...}; checks the N-rank launch path without a GPU (tests/test_bench_launch_cpu.py)')
     a = ap.parse_args()
@@ -435,9 +472,11 @@ def main():
     el = time.perf_counter() - t0
     el = parallel.allreduce_max_float(el, dev)
     last_loss = float(loss[0]) if (a.steps + a.warmup) > 0 else float('nan')
+    if a.dump_outputs and rank == 0:         # before anything below trains the model further
+        dump_outputs(a.dump_outputs, model, loss)
     # the same timed block again (same brackets): `value` stays the FIRST block -- the driver's --steps -- and the spread shows what one sample is worth
     block_values = [world * B * a.steps / max(el, 1e-9)]
-    for _ in range(max(0, a.spread_blocks) if a.steps > 0 else 0):
+    for _ in range(max(0, a.spread_blocks) if a.steps > 0 and a.full else 0):
         torch.cuda.synchronize()
         parallel.barrier()
         torch.cuda.synchronize()
@@ -452,7 +491,7 @@ def main():
 
     # ---- eval throughput (forward + on-device NDCG@3), not part of `value`
     model.eval()
-    ev_steps = a.eval_steps if a.eval_steps >= 0 else max(3, a.steps // 2)
+    ev_steps = (a.eval_steps if a.eval_steps >= 0 else max(3, a.steps // 2)) if a.full else 0
     ev_el, ndcg3 = float('inf'), float('nan')
     if ev_steps > 0:
         for i in range(2 if a.warmup > 0 else 0):
@@ -468,7 +507,7 @@ def main():
 
     # ---- data-parallel exchange timing (N > 1, or a forced one-rank group): a few extra steps with HIP events around every collective
     exchange = None
-    if parallel.active() and eng.overlap_table_update and eng.wide_backward:
+    if a.full and parallel.active() and eng.overlap_table_update and eng.wide_backward:
         eng.time_exchange = True
         for i in range(5):
             one_step(i)
@@ -482,7 +521,7 @@ def main():
 
     # ---- per-kernel profile: EVERY rank runs the same extra steps (they contain the gradient all-reduce)
     prof_shapes, prof_eval, psteps = None, None, 3
-    if not a.no_roofline:
+    if a.full and not a.no_roofline:
         lib = _lib.lib()
         lib.intel_set_concurrency(model._context(), 0)     # price kernels one at a time on one stream
         ov, eng.overlap_table_update = eng.overlap_table_update, False
@@ -521,18 +560,21 @@ def main():
                    'table_adam': ('lazy: torch.optim.Adam\'s dense update of the item-id table, rows without a gradient replayed step by step when they are next '
                                   'gathered (bit-identical to the dense sweep, tests/test_lazy_adam_gpu.py); all rows settled inside the timed region after '
                                   'the last step') if eng._lazy is not None else 'dense sweep over the whole table every step'},
-        'eval_sessions_per_s': round(world * B * ev_steps / ev_el, 1), 'ndcg3_random_init': round(ndcg3, 5),
         'loss_last_step': round(last_loss, 6),
-        'value_spread': {'blocks': [round(v, 1) for v in block_values], 'min': round(min(block_values), 1), 'max': round(max(block_values), 1),
-                         'note': '`value` is the first block (the driver\'s --steps); the others repeat it with the same brackets in the same process'},
     }
+    if a.full:
+        res['eval_sessions_per_s'] = round(world * B * ev_steps / ev_el, 1)
+        res['ndcg3_random_init'] = round(ndcg3, 5)
+        res['value_spread'] = {'blocks': [round(v, 1) for v in block_values], 'min': round(min(block_values), 1), 'max': round(max(block_values), 1),
+                               'note': '`value` is the first block (the driver\'s --steps); the others repeat it with the same brackets in the same process'}
     if exchange is not None:      # data parallel: what the gradient exchange cost and how much of it was NOT hidden (slowest rank, 5 extra steps)
         res['exchange'] = exchange
-    if rank == 0 and not a.no_feed:
+    if a.full and not a.no_feed:
         res['feed'] = feed_throughput(w, cinfo, B, dev)
     bytes_train = algorithmic_bytes_per_session(w['flags'], cinfo, w['batch'], True)
-    res['gather_roofline'] = {'bytes_per_session': bytes_train, 'achieved_GBps': round(bytes_train * res['value'] / world / 1e9, 3),
-                              'peak_GBps': HBM_PEAK / 1e9, 'frac': round(bytes_train * res['value'] / world / HBM_PEAK, 6)}
+    if a.full:
+        res['gather_roofline'] = {'bytes_per_session': bytes_train, 'achieved_GBps': round(bytes_train * res['value'] / world / 1e9, 3),
+                                  'peak_GBps': HBM_PEAK / 1e9, 'frac': round(bytes_train * res['value'] / world / HBM_PEAK, 6)}
     if prof_shapes is not None:
         pmc, pmc_eval, src = None, None, None
         try:        # HBM traffic per launch from the committed rocprofv3 PMC passes (tools/pmc_summary.py)
@@ -592,7 +634,7 @@ def main():
             pass
         res['step_roofline'] = sr
         res['eval_kernel_launches_per_step'] = round(sum(v['launches'] for v in eprof.values()) / psteps, 1)
-    if world == 1 and not bf16 and not a.no_bf16_line:
+    if a.full and world == 1 and not bf16 and not a.no_bf16_line:
         # the same workload in the bf16 arithmetic mode (BASELINE.json configs[1] names it), measured in the same run on the same
         # resident batches: a second model + engine (own fp32 master weights and Adam state), same timing brackets
         # (the fp32 model, its optimizer state and workspace are released first: two resident 1 GB tables + workspaces cost
@@ -650,16 +692,16 @@ def main():
                             'eval_sessions_per_s': round(B * max(1, ev_steps) / ev_bf, 1), 'ndcg3_random_init': round(float(nd_bf.float().nan_to_num(0).mean()), 5),
                             'loss_last_step': round(float(lb[0]), 6) if a.steps else None,
                             'roofline': bf_roof,
-                            'note': 'python bench.py --dtype bf16 gives this mode its own full line (kernel table, eval roofline); not `value`'}
+                            'note': 'python bench.py --full --dtype bf16 gives this mode its own full line (kernel table, eval roofline); not `value`'}
         del eng_bf, model_bf
         gc.collect()
         torch.cuda.empty_cache()
-    if world == 1 and not bf16 and a.workload == 'tmall' and not a.no_workloads:
+    if a.full and world == 1 and not bf16 and a.workload == 'tmall' and not a.no_workloads:
         # the other workloads of BASELINE.json / the published scripts, each as a short timed block in THIS process, so that their numbers are
-        # driver-timed too (own full lines: python bench.py --workload W [--batch B]); never part of `value`
+        # driver-timed too (own full lines: python bench.py --full --workload W [--batch B]); never part of `value`
         res['workloads'] = [short_line(wl, bb, oo, min(20, max(1, a.steps)), min(5, a.warmup), dev)
                             for wl, bb, oo in (('tmall_pub', 512, {}), ('tmall_pub_mse', 512, {'loss': 'IntMSEloss'}), ('lifedata', 2048, {}), ('stress', 256, {}))]
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         res['cpu_baseline'] = cpu_baseline(args_ns, corpus, cinfo, a.workload, a.loss, a.cpu_budget)
     print(json.dumps(res))
 

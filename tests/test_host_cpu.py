@@ -2,7 +2,6 @@
 state_dict compatibility, parameter-slot map, synthetic workloads, data-parallel scheme over gloo."""
 import argparse
 import json
-import os
 
 import numpy as np
 import pytest
@@ -94,32 +93,15 @@ def test_synthetic_batch_layout_and_oracle_consumes_it():
 
 
 def test_reference_default_init_is_reproduced():
-    """Same torch.manual_seed -> same initial weights as the reference (skipped where /root/reference is absent)."""
-    ref_src = '/root/reference/IntEL/src'
-    if not os.path.isdir(ref_src):
-        pytest.skip('reference tree not present on this box')
-    import subprocess
-    import sys
-    code = r'''
-import sys, types, json
-sys.dont_write_bytecode = True
-sys.path.insert(0, %r)
-sys.path.insert(0, %r)
-import numpy as np, torch
-for n, v in (('object', object), ('float', float), ('int', int), ('bool', bool)):
-    if not hasattr(np, n): setattr(np, n, v)
-from tests.helpers import Fixture, make_args, make_corpus
-from models.IntEL.IntEL import IntEL as Ref
-from intel_sigir2023_amd.model import IntEL as Mine
-for name in ('default', 'gru_bpr', 'noxatt'):
-    fx = Fixture(name)
-    a = make_args(fx.args, torch.device('cpu'))
-    torch.manual_seed(5); r = Ref(a, make_corpus(fx.shape)).state_dict()
-    torch.manual_seed(5); m = Mine(a, make_corpus(fx.shape)).state_dict()
-    assert list(r.keys()) == list(m.keys()), name
-    assert all(torch.equal(r[k], m[k]) for k in r), name
-print('same-init-ok')
-''' % (ref_src, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    out = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=300)
-    assert 'same-init-ok' in out.stdout, out.stderr[-2000:]
+    """Same torch.manual_seed -> same initial weights as the reference: a fixture's `sd/` group is the reference model's
+    state_dict right after construction under the fixture's seed (tests/golden/make_golden.py run_config)."""
+    from intel_sigir2023_amd.model import IntEL
+    from tests.helpers import make_args, make_corpus
+    for name in ('default', 'gru_bpr', 'noxatt'):
+        fx = Fixture(name)
+        r = fx.state_dict()
+        torch.manual_seed(json.loads(str(fx['cfg']))['seed'])
+        m = IntEL(make_args(fx.args, torch.device('cpu')), make_corpus(fx.shape)).state_dict()
+        assert list(r.keys()) == list(m.keys()), name
+        assert all(torch.equal(r[k], m[k]) for k in r), name
 

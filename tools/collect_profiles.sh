@@ -7,8 +7,8 @@ tag=${1:-r06}
 out=gpurun_out/$tag
 mkdir -p $out
 export TMPDIR=/tmp
-timeout 900 python bench.py > $out/bench.json 2> $out/bench.err < /dev/null
-PMCARGS="--no_cpu_baseline --no_roofline --no_feed --no_bf16_line --no_workloads --spread_blocks 0"
+timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err < /dev/null
+PMCARGS="--full --no_cpu_baseline --no_roofline --no_feed --no_bf16_line --no_workloads --spread_blocks 0"
 INTEL_STREAMS=0 INTEL_OVERLAP_TABLE=0 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats1s -- python3 bench.py --steps 10 --warmup 3 --eval_steps 0 $PMCARGS > $out/stats1s.log 2>&1 < /dev/null
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --steps 10 --warmup 3 --eval_steps 0 $PMCARGS > $out/stats.log 2>&1 < /dev/null
 INTEL_STREAMS=0 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_eval -- python3 bench.py --steps 0 --warmup 0 --eval_steps 10 $PMCARGS > $out/stats_eval.log 2>&1 < /dev/null
@@ -17,7 +17,7 @@ timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $ou
 timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/fetch_eval -- python3 bench.py --steps 0 --warmup 0 --eval_steps 4 $PMCARGS > $out/fetch_eval.log 2>&1 < /dev/null
 timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $out/write_eval -- python3 bench.py --steps 0 --warmup 0 --eval_steps 4 $PMCARGS > $out/write_eval.log 2>&1 < /dev/null
 # bf16 mode: its own bench line, kernel stats and traffic passes
-timeout 600 python bench.py --dtype bf16 --no_cpu_baseline > $out/bench_bf16.json 2>/dev/null < /dev/null
+timeout 600 python bench.py --full --dtype bf16 --no_cpu_baseline > $out/bench_bf16.json 2>/dev/null < /dev/null
 INTEL_STREAMS=0 INTEL_OVERLAP_TABLE=0 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats1s_bf16 -- python3 bench.py --dtype bf16 --steps 10 --warmup 3 --eval_steps 0 $PMCARGS > $out/stats1s_bf16.log 2>&1 < /dev/null
 timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/fetch_bf16 -- python3 bench.py --dtype bf16 --steps 3 --warmup 1 --eval_steps 0 $PMCARGS > $out/fetch_bf16.log 2>&1 < /dev/null
 timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $out/write_bf16 -- python3 bench.py --dtype bf16 --steps 3 --warmup 1 --eval_steps 0 $PMCARGS > $out/write_bf16.log 2>&1 < /dev/null
@@ -66,29 +66,29 @@ INTEL_PAIR_BWD=0 timeout 600 rocprofv3 --kernel-trace --output-format csv -d $ou
 python3 tools/rocprof_timeline.py $out/trace_nopair 3 > $out/rocprof_timeline_f32_train_nopair.txt 2>&1
 rm -rf $out/trace $out/trace_nopair
 if [ "$2" != "quick" ]; then
-timeout 600 python bench.py --workload tmall_pub --steps 300 --warmup 30 --no_cpu_baseline > $out/bench_tmall_pub_long.json 2>/dev/null < /dev/null
-timeout 600 python bench.py --workload tmall_pub_mse --loss IntMSEloss --steps 300 --warmup 30 --no_cpu_baseline --no_bf16_line --no_feed > $out/bench_tmall_pub_mse.json 2>/dev/null < /dev/null
-INTEL_TOWER32=0 INTEL_HEAD_FUSED=0 timeout 600 python bench.py --workload tmall_pub_mse --loss IntMSEloss --steps 300 --warmup 30 --no_cpu_baseline --no_bf16_line --no_feed --no_roofline > $out/bench_tmall_pub_mse_kernel_per_op.json 2>/dev/null < /dev/null
-timeout 600 python bench.py --workload lifedata --batch 2048 --no_cpu_baseline > $out/bench_lifedata.json 2>/dev/null < /dev/null
-timeout 600 python bench.py --workload stress --batch 256 --steps 20 --warmup 3 --no_cpu_baseline > $out/bench_stress.json 2>/dev/null < /dev/null
-timeout 600 python bench.py --workload stress --batch 1024 --steps 20 --warmup 3 --no_cpu_baseline > $out/bench_stress_b1024.json 2>/dev/null < /dev/null
-timeout 600 python bench.py --workload stress --batch 256 --adam dense --steps 20 --warmup 3 --no_cpu_baseline --no_bf16_line > $out/bench_stress_dense.json 2>/dev/null < /dev/null
-timeout 600 python bench.py --workload stress --batch 1024 --adam dense --steps 20 --warmup 3 --no_cpu_baseline --no_bf16_line > $out/bench_stress_b1024_dense.json 2>/dev/null < /dev/null
-timeout 600 python bench.py --batch 1024 --adam dense --no_cpu_baseline --no_bf16_line --no_feed > $out/bench_tmall_b1024_dense.json 2>/dev/null < /dev/null
-timeout 600 python bench.py --batch 1024 --no_cpu_baseline --no_bf16_line --no_feed > $out/bench_tmall_b1024.json 2>/dev/null < /dev/null
-timeout 600 python bench.py --adam lazy --no_cpu_baseline --no_bf16_line --no_feed > $out/bench_tmall_lazy.json 2>/dev/null < /dev/null
-timeout 600 python bench.py --loss IntListloss --cal_diversity 1 --no_cpu_baseline > $out/bench_pl_div.json 2>/dev/null < /dev/null
-timeout 600 python bench.py --encoder GRU4Rec --no_cpu_baseline > $out/bench_gru4rec.json 2>/dev/null < /dev/null
-timeout 600 python bench.py --workload tmall_pub --no_cpu_baseline > $out/bench_tmall_pub.json 2>/dev/null < /dev/null
-INTEL_GRU_SEQ=0 timeout 600 python bench.py --encoder GRU4Rec --no_cpu_baseline --no_feed > $out/bench_gru4rec_steps.json 2>/dev/null < /dev/null
-INTEL_GRU_SEQ=0 timeout 600 python bench.py --workload tmall_pub --no_cpu_baseline --no_feed > $out/bench_tmall_pub_steps.json 2>/dev/null < /dev/null
-timeout 600 python bench.py --zipf 1 --no_cpu_baseline > $out/bench_zipf.json 2>/dev/null < /dev/null
-INTEL_FUSE_TOWER=0 timeout 600 python bench.py --no_cpu_baseline --no_bf16_line > $out/bench_unfused.json 2>/dev/null < /dev/null
-INTEL_BWD_SCHEDULE=phased timeout 600 python bench.py --no_cpu_baseline --no_bf16_line > $out/bench_phased.json 2>/dev/null < /dev/null
-INTEL_ENC_FUSED=0 timeout 600 python bench.py --no_cpu_baseline > $out/bench_enc_unfused.json 2>/dev/null < /dev/null
-INTEL_ENC_FUSED_BWD=0 timeout 600 python bench.py --no_cpu_baseline --no_bf16_line > $out/bench_enc_unfused_bwd.json 2>/dev/null < /dev/null
-timeout 600 python bench.py --workload lifedata --batch 4096 --no_cpu_baseline > $out/bench_lifedata_b4096.json 2>/dev/null < /dev/null
-for b in 8192 16384 32768; do timeout 600 python bench.py --batch $b --steps 10 --no_cpu_baseline --no_roofline --no_feed --nbatches 4 > $out/bench_b$b.json 2>/dev/null < /dev/null; done
+timeout 600 python bench.py --full --workload tmall_pub --steps 300 --warmup 30 --no_cpu_baseline > $out/bench_tmall_pub_long.json 2>/dev/null < /dev/null
+timeout 600 python bench.py --full --workload tmall_pub_mse --loss IntMSEloss --steps 300 --warmup 30 --no_cpu_baseline --no_bf16_line --no_feed > $out/bench_tmall_pub_mse.json 2>/dev/null < /dev/null
+INTEL_TOWER32=0 INTEL_HEAD_FUSED=0 timeout 600 python bench.py --full --workload tmall_pub_mse --loss IntMSEloss --steps 300 --warmup 30 --no_cpu_baseline --no_bf16_line --no_feed --no_roofline > $out/bench_tmall_pub_mse_kernel_per_op.json 2>/dev/null < /dev/null
+timeout 600 python bench.py --full --workload lifedata --batch 2048 --no_cpu_baseline > $out/bench_lifedata.json 2>/dev/null < /dev/null
+timeout 600 python bench.py --full --workload stress --batch 256 --steps 20 --warmup 3 --no_cpu_baseline > $out/bench_stress.json 2>/dev/null < /dev/null
+timeout 600 python bench.py --full --workload stress --batch 1024 --steps 20 --warmup 3 --no_cpu_baseline > $out/bench_stress_b1024.json 2>/dev/null < /dev/null
+timeout 600 python bench.py --full --workload stress --batch 256 --adam dense --steps 20 --warmup 3 --no_cpu_baseline --no_bf16_line > $out/bench_stress_dense.json 2>/dev/null < /dev/null
+timeout 600 python bench.py --full --workload stress --batch 1024 --adam dense --steps 20 --warmup 3 --no_cpu_baseline --no_bf16_line > $out/bench_stress_b1024_dense.json 2>/dev/null < /dev/null
+timeout 600 python bench.py --full --batch 1024 --adam dense --no_cpu_baseline --no_bf16_line --no_feed > $out/bench_tmall_b1024_dense.json 2>/dev/null < /dev/null
+timeout 600 python bench.py --full --batch 1024 --no_cpu_baseline --no_bf16_line --no_feed > $out/bench_tmall_b1024.json 2>/dev/null < /dev/null
+timeout 600 python bench.py --full --adam lazy --no_cpu_baseline --no_bf16_line --no_feed > $out/bench_tmall_lazy.json 2>/dev/null < /dev/null
+timeout 600 python bench.py --full --loss IntListloss --cal_diversity 1 --no_cpu_baseline > $out/bench_pl_div.json 2>/dev/null < /dev/null
+timeout 600 python bench.py --full --encoder GRU4Rec --no_cpu_baseline > $out/bench_gru4rec.json 2>/dev/null < /dev/null
+timeout 600 python bench.py --full --workload tmall_pub --no_cpu_baseline > $out/bench_tmall_pub.json 2>/dev/null < /dev/null
+INTEL_GRU_SEQ=0 timeout 600 python bench.py --full --encoder GRU4Rec --no_cpu_baseline --no_feed > $out/bench_gru4rec_steps.json 2>/dev/null < /dev/null
+INTEL_GRU_SEQ=0 timeout 600 python bench.py --full --workload tmall_pub --no_cpu_baseline --no_feed > $out/bench_tmall_pub_steps.json 2>/dev/null < /dev/null
+timeout 600 python bench.py --full --zipf 1 --no_cpu_baseline > $out/bench_zipf.json 2>/dev/null < /dev/null
+INTEL_FUSE_TOWER=0 timeout 600 python bench.py --full --no_cpu_baseline --no_bf16_line > $out/bench_unfused.json 2>/dev/null < /dev/null
+INTEL_BWD_SCHEDULE=phased timeout 600 python bench.py --full --no_cpu_baseline --no_bf16_line > $out/bench_phased.json 2>/dev/null < /dev/null
+INTEL_ENC_FUSED=0 timeout 600 python bench.py --full --no_cpu_baseline > $out/bench_enc_unfused.json 2>/dev/null < /dev/null
+INTEL_ENC_FUSED_BWD=0 timeout 600 python bench.py --full --no_cpu_baseline --no_bf16_line > $out/bench_enc_unfused_bwd.json 2>/dev/null < /dev/null
+timeout 600 python bench.py --full --workload lifedata --batch 4096 --no_cpu_baseline > $out/bench_lifedata_b4096.json 2>/dev/null < /dev/null
+for b in 8192 16384 32768; do timeout 600 python bench.py --full --batch $b --steps 10 --no_cpu_baseline --no_roofline --no_feed --nbatches 4 > $out/bench_b$b.json 2>/dev/null < /dev/null; done
 fi
 # keep the merge small: only the summaries travel back
 find $out -name "*.csv" ! -name "*kernel_stats.csv" ! -name "*counter_collection.csv" -delete 2>/dev/null
