@@ -491,6 +491,75 @@ int intel_op_add_layernorm(const float* x, const float* r, int M, int N, const f
                            float* y, float* xhat, float* rstd, void* stream);
 size_t intel_op_workspace_bytes(int M, int N, int K);
 
+/* ---- session / row kernels (exported for unit tests; see tests/test_session_gpu.py) --------
+ * Thin entries over the launchers of csrc/session.hip and csrc/rowops.hip: leading dimensions and column offsets are
+ * passed through unchanged, so a test can use the pitches the model uses.  Entries with a `workspace` build a reduction
+ * queue over it and flush it before returning (size: the `*_workspace_bytes` companion). */
+/* Single-query cross-attention pooling (modules/attention.py:55-62 with L_q = 1; IntEL.py:201-204): att = scale <qk_b, x_l>
+ * over ALL L rows, minus its max over all L rows, rows l >= session_len masked, softmax, NaN -> 0; xbar = sum_l attw_l x_l.
+ * x [B, L, d], qk [B, d], xbar [B, d], attw [B, L].  gamma / beta non-NULL (d = 64 / 128, L <= 100): x holds the x-hat
+ * stash of a LayerNorm and the rows are x-hat * gamma + beta (IntEL.py:187,196). */
+int intel_op_xatt_pool_fwd(const float* x, int B, int L, int d, const float* qk, const int* session_len, float scale, const float* gamma,
+                           const float* beta, float* xbar, float* attw, void* stream);
+/* Its backward under autograd: dxbar [B, ldxb] -> dx [B, L, d] (all L rows written), dqk [B, d]. */
+int intel_op_xatt_pool_bwd(const float* x, int B, int L, int d, const float* qk, const float* attw, const float* dxbar, int ldxb, float scale,
+                           float* dx, float* dqk, void* stream);
+/* The same fused with the backward of the LayerNorm that produced x (IntEL.py:187,196 -> :201-204 under autograd): xhat
+ * [B, L, d], rstd [B*L]; writes dz [B, L, d], dqk [B, d]; dgamma / dbeta [d] (+)= column sums. */
+size_t intel_op_xatt_pool_ln_bwd_workspace_bytes(int B, int d);
+int intel_op_xatt_pool_ln_bwd(const float* xhat, const float* rstd, const float* gamma, const float* beta, int B, int L, int d, const float* qk,
+                              const float* attw, const float* dxbar, int ldxb, float scale, float* dz, float* dqk, float* dgamma, float* dbeta,
+                              int accumulate, void* workspace, size_t workspace_bytes, void* stream);
+/* Fusion weights and score aggregation (IntEL.py:212-215): weights[b,l,:] = l < session_len ? wv[b,:] : wpad[b,:] (per_item != 0:
+ * weights [B, L, K] is an input), ens[b,l] = sum_k weights * scores. */
+int intel_op_ens_fwd(const float* wv, const float* wpad, const float* scores, const int* session_len, int B, int L, int K, int per_item,
+                     float* weights, float* ens, void* stream);
+/* Its backward: dwt = d_weights + d_ens * scores (either may be NULL); dwv / dwpad [B, K] = its sums over l < session_len /
+ * l >= session_len; per_item != 0: dwt [B, L, K] is written instead. */
+int intel_op_ens_bwd(const float* d_weights, const float* d_ens, const float* scores, const int* session_len, int B, int L, int K, int per_item,
+                     float* dwv, float* dwpad, float* dwt, void* stream);
+/* Attention of the ONE query row of a session's last valid position (models/GeneralSeq.py:100-105 with modules/layers.py:50-60):
+ * kv [rows, 2*dm] = [k | v], q [B, dm], out [B, dm], P [B*heads, T].  row_off NULL: padded rows b*T + t; else packed rows
+ * row_off[b] + t, t < len[b]. */
+int intel_op_attn_lastq_fwd(const float* kv, const float* q, const int* len, const int* row_off, int B, int T, int dm, int heads, float* out,
+                            float* P, void* stream);
+/* Its backward: dq [B, dm], dkv like kv (padded: all T rows written, zeros beyond len; packed: the session's len rows only). */
+int intel_op_attn_lastq_bwd(const float* kv, const float* q, const float* P, const float* d_out, const int* len, const int* row_off, int B,
+                            int T, int dm, int heads, float* dq, float* dkv, void* stream);
+/* out[b, col0:col0+dm] = E[row of position len[b]-1] (GeneralSeq.py:103-105); len[b] == 0: zeros. */
+int intel_op_select_last(const float* E, int dm, const int* len, const int* row_off, int B, int T, float* out, int ldo, int col0, void* stream);
+/* Its backward: dX[row of position len[b]-1, :] += src[b, 0:dm]; len[b] == 0: nothing is added. */
+int intel_op_add_at_last(const float* src, int lds, int dm, const int* len, const int* row_off, int B, int T, float* dX, void* stream);
+/* torch.nn.LayerNorm backward from the x-hat / rstd stash (IntEL.py:187,196 under autograd): dz [M, lddz]; dgamma / dbeta [N]
+ * (+)= column sums.  queued != 0: the column sums go through a reduction queue, else through the immediate reduction. */
+size_t intel_op_layernorm_bwd_workspace_bytes(int M, int N);
+int intel_op_layernorm_bwd(const float* dy, int lddy, const float* xhat, int ldxh, const float* rstd, int M, int N, const float* gamma, float* dz,
+                           int lddz, float* dgamma, float* dbeta, int accumulate, int queued, void* workspace, size_t workspace_bytes,
+                           void* stream);
+/* y = softmax(x, -1) over rows of length N (IntEL.py:153), in place allowed; dx = y * (dy - sum(dy * y)), dx may alias dy. */
+int intel_op_softmax_rows(const float* x, int M, int N, float* y, void* stream);
+int intel_op_softmax_rows_bwd(const float* y, const float* dy, int M, int N, float* dx, void* stream);
+/* torch.nn.Embedding backward (IntEL.py:170-173 under autograd): grad_table[idx[m], :] += src[m, col0:col0+d] (* (relu_out[m, rcol0 + c] > 0)
+ * when relu_out is given); idx < 0 is skipped; row_flags[idx[m]] = 1 (optional). */
+int intel_op_scatter_add_rows(const float* src, int lds, int col0, int d, const int* idx, int M, float* grad_table, const float* relu_out,
+                              int ldr, int rcol0, unsigned char* row_flags, void* stream);
+/* The same from (id, source row) pairs sorted by id (d = 16 / 32 / 64 / 128).  row_off / len / T non-NULL: pair row b*T + t reads the
+ * packed source row row_off[b] + t, positions t >= len[b] are skipped. */
+int intel_op_scatter_add_sorted(const float* src, int lds, int col0, int d, const int* sorted_ids, const int* sorted_rows, int n,
+                                float* grad_table, unsigned char* row_flags, const int* row_off, const int* len, int T, void* stream);
+/* --cross_attention 0 gating (IntEL.py:206-209): dst[m, col0 + c] = x[m, c] * vec[b, c]; backward: dx = dfeat * vec, dvec = sum_l dfeat * x. */
+int intel_op_gate_fwd(const float* x, int d, const float* vec, int B, int L, float* dst, int ldd, int col0, void* stream);
+int intel_op_gate_bwd(const float* dfeat, int ldf, int col0, const float* x, int d, const float* vec, int B, int L, float* dx, float* dvec,
+                      void* stream);
+/* Mean-pooled gate (models/supervise/aWELv_IntEL.py:188-197): xbar = mean_l x, feat[b, col0 + c] = xbar * vec; backward:
+ * dx[b, l, c] = dfeat * vec / L, dvec = dfeat * xbar. */
+int intel_op_gate_mean_fwd(const float* x, int d, const float* vec, int B, int L, float* xbar, float* feat, int ldf, int col0, void* stream);
+int intel_op_gate_mean_bwd(const float* dfeat, int ldf, int col0, const float* xbar, int d, const float* vec, int B, int L, float* dx,
+                           float* dvec, void* stream);
+/* out[b, ocol0 + c] (+)= sum_l src[b*L + l, col0 + c]: the gradient of a per-session vector broadcast over the list (IntEL.py:210). */
+int intel_op_session_colsum(const float* src, int lds, int col0, int d, int B, int L, float* out, int ldo, int ocol0, int accumulate,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,6 +135,11 @@ EXPORTS = [
     'intel_op_linear_dgrad', 'intel_op_linear_wgrad', 'intel_op_linear_bwd', 'intel_op_linear_bwd_workspace_bytes', 'intel_op_linear_bwd_qkv', 'intel_op_linear_bwd_qkv_workspace_bytes', 'intel_op_attention', 'intel_op_attention_bwd', 'intel_op_attention_bwd_workspace_bytes',
     'intel_op_add_layernorm', 'intel_op_workspace_bytes', 'intel_prof_enable', 'intel_prof_collect', 'intel_prof_timeline', 'intel_feed_collate', 'intel_feed_abi_sizes', 'intel_rows_take', 'intel_rows_add', 'intel_rows_compact', 'intel_rows_compact_scratch_ints', 'intel_rows_mark',
     'intel_lazy_table_sizeof', 'intel_adam_lazy_step', 'intel_adam_lazy_catchup', 'intel_adam_lazy_flush', 'intel_set_lazy_table',
+    # session / row kernels (tests/test_session_gpu.py)
+    'intel_op_xatt_pool_fwd', 'intel_op_xatt_pool_bwd', 'intel_op_xatt_pool_ln_bwd', 'intel_op_xatt_pool_ln_bwd_workspace_bytes', 'intel_op_ens_fwd', 'intel_op_ens_bwd',
+    'intel_op_attn_lastq_fwd', 'intel_op_attn_lastq_bwd', 'intel_op_select_last', 'intel_op_add_at_last', 'intel_op_layernorm_bwd', 'intel_op_layernorm_bwd_workspace_bytes',
+    'intel_op_softmax_rows', 'intel_op_softmax_rows_bwd', 'intel_op_scatter_add_rows', 'intel_op_scatter_add_sorted', 'intel_op_gate_fwd', 'intel_op_gate_bwd',
+    'intel_op_gate_mean_fwd', 'intel_op_gate_mean_bwd', 'intel_op_session_colsum',
 ]
 
 
@@ -191,6 +196,27 @@ def _declare(l):
     sig('intel_op_attention_bwd_workspace_bytes', sz, [i, i, i, i])
     sig('intel_op_add_layernorm', i, [vp, vp, i, i, vp, vp, vp, vp, vp, vp])
     sig('intel_op_workspace_bytes', sz, [i, i, i])
+    sig('intel_op_xatt_pool_fwd', i, [vp, i, i, i, vp, vp, f, vp, vp, vp, vp, vp])
+    sig('intel_op_xatt_pool_bwd', i, [vp, i, i, i, vp, vp, vp, i, f, vp, vp, vp])
+    sig('intel_op_xatt_pool_ln_bwd_workspace_bytes', sz, [i, i])
+    sig('intel_op_xatt_pool_ln_bwd', i, [vp, vp, vp, vp, i, i, i, vp, vp, vp, i, f, vp, vp, vp, vp, i, vp, sz, vp])
+    sig('intel_op_ens_fwd', i, [vp, vp, vp, vp, i, i, i, i, vp, vp, vp])
+    sig('intel_op_ens_bwd', i, [vp, vp, vp, vp, i, i, i, i, vp, vp, vp, vp])
+    sig('intel_op_attn_lastq_fwd', i, [vp, vp, vp, vp, i, i, i, i, vp, vp, vp])
+    sig('intel_op_attn_lastq_bwd', i, [vp, vp, vp, vp, vp, vp, i, i, i, i, vp, vp, vp])
+    sig('intel_op_select_last', i, [vp, i, vp, vp, i, i, vp, i, i, vp])
+    sig('intel_op_add_at_last', i, [vp, i, i, vp, vp, i, i, vp, vp])
+    sig('intel_op_layernorm_bwd_workspace_bytes', sz, [i, i])
+    sig('intel_op_layernorm_bwd', i, [vp, i, vp, i, vp, i, i, vp, vp, i, vp, vp, i, i, vp, sz, vp])
+    sig('intel_op_softmax_rows', i, [vp, i, i, vp, vp])
+    sig('intel_op_softmax_rows_bwd', i, [vp, vp, i, i, vp, vp])
+    sig('intel_op_scatter_add_rows', i, [vp, i, i, i, vp, i, vp, vp, i, i, vp, vp])
+    sig('intel_op_scatter_add_sorted', i, [vp, i, i, i, vp, vp, i, vp, vp, vp, vp, i, vp])
+    sig('intel_op_gate_fwd', i, [vp, i, vp, i, i, vp, i, i, vp])
+    sig('intel_op_gate_bwd', i, [vp, i, i, vp, i, vp, i, i, vp, vp, vp])
+    sig('intel_op_gate_mean_fwd', i, [vp, i, vp, i, i, vp, vp, i, i, vp])
+    sig('intel_op_gate_mean_bwd', i, [vp, i, i, vp, i, vp, i, i, vp, vp, vp])
+    sig('intel_op_session_colsum', i, [vp, i, i, i, i, i, vp, i, i, i, vp])
     sig('intel_rows_take', i, [vp, i, vp, i, vp, i, vp])
     sig('intel_rows_add', i, [vp, i, vp, i, vp, vp])
     sig('intel_rows_compact', i, [vp, C.c_longlong, vp, i, vp, vp])

@@ -292,3 +292,153 @@ extern "C" int intel_loss_total(const float* ensemble_loss, const double* intent
   INTEL_CHECK_ARG(ensemble_loss && out3, "loss_total: null tensor");
   return launch_loss_total(ensemble_loss, intent_out3, ensemble_weight, intent_weight, out3, (hipStream_t)stream);
 }
+
+// ---- session / row kernels (session.hip, rowops.hip): thin entries for the unit tests ---------------------------------
+// a reduction queue over a caller-supplied arena, flushed before the entry returns
+static size_t op_arena_bytes(size_t slab_floats) { return (slab_floats + 64) * sizeof(float); }
+template <class F>
+static int with_queue(void* workspace, size_t workspace_bytes, size_t slab_floats, hipStream_t st, const char* what, F&& launch) {
+  INTEL_CHECK_ARG(workspace && workspace_bytes >= op_arena_bytes(slab_floats), "%s: workspace too small", what);
+  ReduceQueue* q = redq_create();
+  INTEL_CHECK_ARG(q != nullptr, "%s: out of memory", what);
+  redq_reset(q, (float*)workspace, slab_floats + 64);
+  int rc = launch(q);
+  if (rc == 0) rc = redq_flush(q, st);
+  redq_destroy(q);
+  return rc;
+}
+
+extern "C" int intel_op_xatt_pool_fwd(const float* x, int B, int L, int d, const float* qk, const int* session_len, float scale,
+                                      const float* gamma, const float* beta, float* xbar, float* attw, void* stream) {
+  INTEL_CHECK_ARG(x && qk && session_len && xbar && attw && L > 0 && d > 0 && (!gamma == !beta), "op_xatt_pool_fwd: bad argument");
+  return launch_xatt_pool_fwd(x, B, L, d, qk, session_len, scale, xbar, attw, (hipStream_t)stream, gamma, beta);
+}
+
+extern "C" int intel_op_xatt_pool_bwd(const float* x, int B, int L, int d, const float* qk, const float* attw, const float* dxbar, int ldxb,
+                                      float scale, float* dx, float* dqk, void* stream) {
+  INTEL_CHECK_ARG(x && qk && attw && dxbar && dx && dqk && L > 0 && d > 0 && d % 4 == 0 && ldxb >= d && (ldxb & 3) == 0, "op_xatt_pool_bwd: bad argument");
+  return launch_xatt_pool_bwd(x, B, L, d, qk, attw, dxbar, ldxb, scale, dx, dqk, (hipStream_t)stream);
+}
+
+extern "C" size_t intel_op_xatt_pool_ln_bwd_workspace_bytes(int B, int d) {
+  if (B <= 0 || d <= 0) return 0;
+  return op_arena_bytes(xatt_ln_bwd_slab_floats(B, d));
+}
+extern "C" int intel_op_xatt_pool_ln_bwd(const float* xhat, const float* rstd, const float* gamma, const float* beta, int B, int L, int d,
+                                         const float* qk, const float* attw, const float* dxbar, int ldxb, float scale, float* dz, float* dqk,
+                                         float* dgamma, float* dbeta, int accumulate, void* workspace, size_t workspace_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  INTEL_CHECK_ARG(xhat && rstd && gamma && beta && qk && attw && dxbar && dz && dqk && dgamma && dbeta && B > 0 && ldxb >= d,
+                  "op_xatt_pool_ln_bwd: bad argument");
+  return with_queue(workspace, workspace_bytes, xatt_ln_bwd_slab_floats(B, d), st, "op_xatt_pool_ln_bwd", [&](ReduceQueue* q) {
+    return launch_xatt_pool_ln_bwd(xhat, rstd, gamma, beta, B, L, d, qk, attw, dxbar, ldxb, scale, dz, dqk, dgamma, dbeta, accumulate, st, q);
+  });
+}
+
+extern "C" int intel_op_ens_fwd(const float* wv, const float* wpad, const float* scores, const int* session_len, int B, int L, int K,
+                                int per_item, float* weights, float* ens, void* stream) {
+  INTEL_CHECK_ARG(scores && session_len && weights && ens && (per_item || (wv && wpad)) && L > 0 && K > 0, "op_ens_fwd: bad argument");
+  return launch_ens_fwd(wv, wpad, scores, session_len, B, L, K, per_item, weights, ens, (hipStream_t)stream);
+}
+
+extern "C" int intel_op_ens_bwd(const float* d_weights, const float* d_ens, const float* scores, const int* session_len, int B, int L, int K,
+                                int per_item, float* dwv, float* dwpad, float* dwt, void* stream) {
+  INTEL_CHECK_ARG(session_len && (scores || !d_ens) && (per_item ? dwt != nullptr : (dwv && dwpad)) && L > 0 && K > 0, "op_ens_bwd: bad argument");
+  return launch_ens_bwd(d_weights, d_ens, scores, session_len, B, L, K, per_item, dwv, dwpad, dwt, (hipStream_t)stream);
+}
+
+extern "C" int intel_op_attn_lastq_fwd(const float* kv, const float* q, const int* len, const int* row_off, int B, int T, int dm, int heads,
+                                       float* out, float* P, void* stream) {
+  INTEL_CHECK_ARG(kv && q && len && out && P && T > 0 && dm > 0 && heads > 0, "op_attn_lastq_fwd: bad argument");
+  return launch_attn_lastq_fwd(kv, q, len, B, T, dm, heads, out, P, (hipStream_t)stream, row_off);
+}
+
+extern "C" int intel_op_attn_lastq_bwd(const float* kv, const float* q, const float* P, const float* d_out, const int* len, const int* row_off,
+                                       int B, int T, int dm, int heads, float* dq, float* dkv, void* stream) {
+  INTEL_CHECK_ARG(kv && q && P && d_out && len && dq && dkv && T > 0 && dm > 0 && heads > 0 && dm % heads == 0 && (dm / heads) % 4 == 0,
+                  "op_attn_lastq_bwd: bad argument");
+  return launch_attn_lastq_bwd(kv, q, P, d_out, len, B, T, dm, heads, dq, dkv, (hipStream_t)stream, row_off);
+}
+
+extern "C" int intel_op_select_last(const float* E, int dm, const int* len, const int* row_off, int B, int T, float* out, int ldo, int col0,
+                                    void* stream) {
+  INTEL_CHECK_ARG(E && len && out && dm > 0 && T > 0 && col0 >= 0 && ldo >= col0 + dm, "op_select_last: bad argument");
+  return launch_select_last(E, dm, len, B, T, out, ldo, col0, (hipStream_t)stream, row_off);
+}
+
+extern "C" int intel_op_add_at_last(const float* src, int lds, int dm, const int* len, const int* row_off, int B, int T, float* dX, void* stream) {
+  INTEL_CHECK_ARG(src && len && dX && dm > 0 && T > 0 && lds >= dm, "op_add_at_last: bad argument");
+  return launch_add_at_last(src, lds, dm, len, B, T, dX, (hipStream_t)stream, row_off);
+}
+
+extern "C" size_t intel_op_layernorm_bwd_workspace_bytes(int M, int N) {
+  if (M <= 0 || N <= 0) return 0;
+  return op_arena_bytes(ln_bwd_slab_floats(M, N));
+}
+extern "C" int intel_op_layernorm_bwd(const float* dy, int lddy, const float* xhat, int ldxh, const float* rstd, int M, int N, const float* gamma,
+                                      float* dz, int lddz, float* dgamma, float* dbeta, int accumulate, int queued, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  INTEL_CHECK_ARG(dy && xhat && rstd && gamma && dz && dgamma && dbeta && M > 0 && N > 0 && lddy >= N && ldxh >= N && lddz >= N,
+                  "op_layernorm_bwd: bad argument");
+  if (!queued) {
+    INTEL_CHECK_ARG(workspace && workspace_bytes >= ln_bwd_slab_floats(M, N) * sizeof(float), "op_layernorm_bwd: workspace too small");
+    return launch_layernorm_bwd(dy, lddy, xhat, ldxh, rstd, M, N, gamma, dz, lddz, dgamma, dbeta, accumulate, (float*)workspace, st, nullptr);
+  }
+  return with_queue(workspace, workspace_bytes, ln_bwd_slab_floats(M, N), st, "op_layernorm_bwd", [&](ReduceQueue* q) {
+    return launch_layernorm_bwd(dy, lddy, xhat, ldxh, rstd, M, N, gamma, dz, lddz, dgamma, dbeta, accumulate, nullptr, st, q);
+  });
+}
+
+extern "C" int intel_op_softmax_rows(const float* x, int M, int N, float* y, void* stream) {
+  INTEL_CHECK_ARG(x && y && N > 0, "op_softmax_rows: bad argument");
+  return launch_softmax_rows(x, M, N, y, (hipStream_t)stream);
+}
+
+extern "C" int intel_op_softmax_rows_bwd(const float* y, const float* dy, int M, int N, float* dx, void* stream) {
+  INTEL_CHECK_ARG(y && dy && dx && N > 0, "op_softmax_rows_bwd: bad argument");
+  return launch_softmax_rows_bwd(y, dy, M, N, dx, (hipStream_t)stream);
+}
+
+extern "C" int intel_op_scatter_add_rows(const float* src, int lds, int col0, int d, const int* idx, int M, float* grad_table,
+                                         const float* relu_out, int ldr, int rcol0, unsigned char* row_flags, void* stream) {
+  INTEL_CHECK_ARG(src && idx && grad_table && d > 0 && col0 >= 0 && lds >= col0 + d && (!relu_out || (rcol0 >= 0 && ldr >= rcol0 + d)),
+                  "op_scatter_add_rows: bad argument");
+  return launch_scatter_add_rows(src, lds, col0, d, idx, M, grad_table, relu_out, ldr, rcol0, (hipStream_t)stream, row_flags);
+}
+
+extern "C" int intel_op_scatter_add_sorted(const float* src, int lds, int col0, int d, const int* sorted_ids, const int* sorted_rows, int n,
+                                           float* grad_table, unsigned char* row_flags, const int* row_off, const int* len, int T, void* stream) {
+  INTEL_CHECK_ARG(src && sorted_ids && sorted_rows && grad_table && col0 >= 0 && lds >= col0 + d && (!row_off || (len && T > 0)),
+                  "op_scatter_add_sorted: bad argument");
+  return launch_scatter_add_sorted(src, lds, col0, d, sorted_ids, sorted_rows, n, grad_table, (hipStream_t)stream, row_flags, row_off, len, T);
+}
+
+extern "C" int intel_op_gate_fwd(const float* x, int d, const float* vec, int B, int L, float* dst, int ldd, int col0, void* stream) {
+  INTEL_CHECK_ARG(x && vec && dst && d > 0 && col0 >= 0 && ldd >= col0 + d, "op_gate_fwd: bad argument");
+  return launch_gate_fwd(x, d, vec, B, L, dst, ldd, col0, (hipStream_t)stream);
+}
+
+extern "C" int intel_op_gate_bwd(const float* dfeat, int ldf, int col0, const float* x, int d, const float* vec, int B, int L, float* dx,
+                                 float* dvec, void* stream) {
+  INTEL_CHECK_ARG(dfeat && x && vec && dx && dvec && d > 0 && col0 >= 0 && ldf >= col0 + d, "op_gate_bwd: bad argument");
+  return launch_gate_bwd(dfeat, ldf, col0, x, d, vec, B, L, dx, dvec, (hipStream_t)stream);
+}
+
+extern "C" int intel_op_gate_mean_fwd(const float* x, int d, const float* vec, int B, int L, float* xbar, float* feat, int ldf, int col0,
+                                      void* stream) {
+  INTEL_CHECK_ARG(x && vec && xbar && feat && d > 0 && L > 0 && col0 >= 0 && ldf >= col0 + d, "op_gate_mean_fwd: bad argument");
+  return launch_gate_mean_fwd(x, d, vec, B, L, xbar, feat, ldf, col0, (hipStream_t)stream);
+}
+
+extern "C" int intel_op_gate_mean_bwd(const float* dfeat, int ldf, int col0, const float* xbar, int d, const float* vec, int B, int L, float* dx,
+                                      float* dvec, void* stream) {
+  INTEL_CHECK_ARG(dfeat && xbar && vec && dx && dvec && d > 0 && L > 0 && col0 >= 0 && ldf >= col0 + d, "op_gate_mean_bwd: bad argument");
+  return launch_gate_mean_bwd(dfeat, ldf, col0, xbar, d, vec, B, L, dx, dvec, (hipStream_t)stream);
+}
+
+extern "C" int intel_op_session_colsum(const float* src, int lds, int col0, int d, int B, int L, float* out, int ldo, int ocol0, int accumulate,
+                                       void* stream) {
+  INTEL_CHECK_ARG(src && out && d > 0 && col0 >= 0 && lds >= col0 + d && ocol0 >= 0 && ldo >= ocol0 + d, "op_session_colsum: bad argument");
+  return launch_session_colsum(src, lds, col0, d, B, L, out, ldo, ocol0, accumulate, (hipStream_t)stream);
+}

@@ -102,6 +102,178 @@ def add_layernorm(x, r, gamma, beta, stash=False):
 
 
 # ------------------------------------------------------------------------------------------------------------------------
+# session / row kernels (csrc/session.hip, csrc/rowops.hip) for the unit tests (tests/test_session_gpu.py).  ctypes only: they
+# are not dispatcher ops.  Buffers with a pitch (`ld*`) and a column offset (`col0`) are passed as the caller allocated them.
+# ------------------------------------------------------------------------------------------------------------------------
+def _f32(shape, like):
+    return torch.empty(shape, dtype=torch.float32, device=like.device)
+
+
+def xatt_pool_fwd(x, qk, session_len, scale, gamma=None, beta=None):
+    """x [B, L, d] (or its x-hat stash with gamma / beta), qk [B, d], session_len int32 [B] -> xbar [B, d], attw [B, L]."""
+    B, Lm, d = x.shape
+    xbar, attw = _f32((B, d), x), _f32((B, Lm), x)
+    L.check(L.lib().intel_op_xatt_pool_fwd(L.ptr(x), B, Lm, d, L.ptr(qk), L.ptr(session_len), float(scale), L.ptr(gamma), L.ptr(beta), L.ptr(xbar),
+                                           L.ptr(attw), L.stream_ptr(x.device)), 'intel_op_xatt_pool_fwd')
+    return xbar, attw
+
+
+def xatt_pool_bwd(x, qk, attw, dxbar, scale):
+    """dxbar [B, ldxb] (the first d columns are used) -> dx [B, L, d], dqk [B, d]."""
+    B, Lm, d = x.shape
+    dx, dqk = torch.empty_like(x), _f32((B, d), x)
+    L.check(L.lib().intel_op_xatt_pool_bwd(L.ptr(x), B, Lm, d, L.ptr(qk), L.ptr(attw), L.ptr(dxbar), dxbar.shape[1], float(scale), L.ptr(dx), L.ptr(dqk),
+                                           L.stream_ptr(x.device)), 'intel_op_xatt_pool_bwd')
+    return dx, dqk
+
+
+def xatt_pool_ln_bwd(xhat, rstd, gamma, beta, qk, attw, dxbar, scale, dgamma, dbeta, accumulate=False):
+    """The pooling backward fused with the LayerNorm backward: -> dz [B, L, d], dqk [B, d]; dgamma / dbeta [d] written or accumulated in place."""
+    B, Lm, d = xhat.shape
+    dz, dqk = torch.empty_like(xhat), _f32((B, d), xhat)
+    nb = L.lib().intel_op_xatt_pool_ln_bwd_workspace_bytes(B, d)
+    ws = _ws(nb, xhat.device)
+    L.check(L.lib().intel_op_xatt_pool_ln_bwd(L.ptr(xhat), L.ptr(rstd), L.ptr(gamma), L.ptr(beta), B, Lm, d, L.ptr(qk), L.ptr(attw), L.ptr(dxbar),
+                                              dxbar.shape[1], float(scale), L.ptr(dz), L.ptr(dqk), L.ptr(dgamma), L.ptr(dbeta), int(accumulate), L.ptr(ws),
+                                              nb, L.stream_ptr(xhat.device)), 'intel_op_xatt_pool_ln_bwd')
+    return dz, dqk
+
+
+def ens_fwd(scores, session_len, wv=None, wpad=None, weights=None):
+    """scores [B, L, K]; wv / wpad [B, K] (session weights) or weights [B, L, K] (per item) -> weights, ens [B, L]."""
+    B, Lm, K = scores.shape
+    per_item = weights is not None
+    if not per_item:
+        weights = torch.empty_like(scores)
+    ens = _f32((B, Lm), scores)
+    L.check(L.lib().intel_op_ens_fwd(L.ptr(wv), L.ptr(wpad), L.ptr(scores), L.ptr(session_len), B, Lm, K, int(per_item), L.ptr(weights), L.ptr(ens),
+                                     L.stream_ptr(scores.device)), 'intel_op_ens_fwd')
+    return weights, ens
+
+
+def ens_bwd(scores, session_len, d_weights=None, d_ens=None, per_item=False):
+    """-> (dwv, dwpad) [B, K] each, or dwt [B, L, K] when per_item."""
+    B, Lm, K = scores.shape
+    dwv = dwpad = dwt = None
+    if per_item:
+        dwt = torch.empty_like(scores)
+    else:
+        dwv, dwpad = _f32((B, K), scores), _f32((B, K), scores)
+    L.check(L.lib().intel_op_ens_bwd(L.ptr(d_weights), L.ptr(d_ens), L.ptr(scores), L.ptr(session_len), B, Lm, K, int(per_item), L.ptr(dwv), L.ptr(dwpad),
+                                     L.ptr(dwt), L.stream_ptr(scores.device)), 'intel_op_ens_bwd')
+    return dwt if per_item else (dwv, dwpad)
+
+
+def attn_lastq_fwd(kv, q, length, T, heads, row_off=None):
+    """kv [rows, 2*dm] (padded: rows = B*T; packed: row_off[b] + t), q [B, dm] -> out [B, dm], P [B*heads, T]."""
+    B, dm = q.shape
+    out, P = torch.empty_like(q), _f32((B * heads, T), q)
+    L.check(L.lib().intel_op_attn_lastq_fwd(L.ptr(kv), L.ptr(q), L.ptr(length), L.ptr(row_off), B, T, dm, heads, L.ptr(out), L.ptr(P),
+                                            L.stream_ptr(q.device)), 'intel_op_attn_lastq_fwd')
+    return out, P
+
+
+def attn_lastq_bwd(kv, q, P, d_out, length, T, heads, dkv, row_off=None):
+    """-> dq [B, dm]; dkv (same layout as kv) is written in place."""
+    B, dm = q.shape
+    dq = torch.empty_like(q)
+    L.check(L.lib().intel_op_attn_lastq_bwd(L.ptr(kv), L.ptr(q), L.ptr(P), L.ptr(d_out), L.ptr(length), L.ptr(row_off), B, T, dm, heads, L.ptr(dq),
+                                            L.ptr(dkv), L.stream_ptr(q.device)), 'intel_op_attn_lastq_bwd')
+    return dq
+
+
+def select_last(E, length, T, out, col0, row_off=None):
+    """out[b, col0:col0+dm] = E[row of position length[b]-1] (in place on `out` [B, ldo])."""
+    dm, B = E.shape[1], length.shape[0]
+    L.check(L.lib().intel_op_select_last(L.ptr(E), dm, L.ptr(length), L.ptr(row_off), B, T, L.ptr(out), out.shape[1], col0, L.stream_ptr(E.device)),
+            'intel_op_select_last')
+    return out
+
+
+def add_at_last(src, dm, length, T, dX, row_off=None):
+    """dX[row of position length[b]-1, :] += src[b, 0:dm] (in place on dX [rows, dm]; src [B, lds])."""
+    B = length.shape[0]
+    L.check(L.lib().intel_op_add_at_last(L.ptr(src), src.shape[1], dm, L.ptr(length), L.ptr(row_off), B, T, L.ptr(dX), L.stream_ptr(src.device)),
+            'intel_op_add_at_last')
+    return dX
+
+
+def layernorm_bwd(dy, xhat, rstd, N, gamma, dz, dgamma, dbeta, accumulate=False, queued=True):
+    """dy / xhat / dz [M, pitch >= N] with their own pitches; dz is written in place, dgamma / dbeta [N] written or accumulated in place."""
+    M = dy.shape[0]
+    nb = L.lib().intel_op_layernorm_bwd_workspace_bytes(M, N)
+    ws = _ws(nb, dy.device)
+    L.check(L.lib().intel_op_layernorm_bwd(L.ptr(dy), dy.shape[1], L.ptr(xhat), xhat.shape[1], L.ptr(rstd), M, N, L.ptr(gamma), L.ptr(dz), dz.shape[1],
+                                           L.ptr(dgamma), L.ptr(dbeta), int(accumulate), int(queued), L.ptr(ws), nb, L.stream_ptr(dy.device)),
+            'intel_op_layernorm_bwd')
+    return dz, dgamma, dbeta
+
+
+def softmax_rows(x, out=None):
+    M, N = x.shape
+    y = torch.empty_like(x) if out is None else out
+    L.check(L.lib().intel_op_softmax_rows(L.ptr(x), M, N, L.ptr(y), L.stream_ptr(x.device)), 'intel_op_softmax_rows')
+    return y
+
+
+def softmax_rows_bwd(y, dy, out=None):
+    M, N = y.shape
+    dx = torch.empty_like(y) if out is None else out
+    L.check(L.lib().intel_op_softmax_rows_bwd(L.ptr(y), L.ptr(dy), M, N, L.ptr(dx), L.stream_ptr(y.device)), 'intel_op_softmax_rows_bwd')
+    return dx
+
+
+def scatter_add_rows(src, col0, d, idx, table, relu_out=None, rcol0=0, row_flags=None):
+    """table[idx[m], :] += src[m, col0:col0+d] (* (relu_out[m, rcol0:rcol0+d] > 0)); in place on table [rows, d]."""
+    L.check(L.lib().intel_op_scatter_add_rows(L.ptr(src), src.shape[1], col0, d, L.ptr(idx), idx.numel(), L.ptr(table), L.ptr(relu_out),
+                                              relu_out.shape[1] if relu_out is not None else 0, rcol0, L.ptr(row_flags), L.stream_ptr(src.device)),
+            'intel_op_scatter_add_rows')
+    return table
+
+
+def scatter_add_sorted(src, col0, d, sorted_ids, sorted_rows, table, row_flags=None, row_off=None, length=None, T=0):
+    L.check(L.lib().intel_op_scatter_add_sorted(L.ptr(src), src.shape[1], col0, d, L.ptr(sorted_ids), L.ptr(sorted_rows), sorted_ids.numel(), L.ptr(table),
+                                                L.ptr(row_flags), L.ptr(row_off), L.ptr(length), T, L.stream_ptr(src.device)), 'intel_op_scatter_add_sorted')
+    return table
+
+
+def gate_fwd(x, vec, dst, col0):
+    B, Lm, d = x.shape
+    L.check(L.lib().intel_op_gate_fwd(L.ptr(x), d, L.ptr(vec), B, Lm, L.ptr(dst), dst.shape[1], col0, L.stream_ptr(x.device)), 'intel_op_gate_fwd')
+    return dst
+
+
+def gate_bwd(dfeat, col0, x, vec):
+    B, Lm, d = x.shape
+    dx, dvec = torch.empty_like(x), torch.empty_like(vec)
+    L.check(L.lib().intel_op_gate_bwd(L.ptr(dfeat), dfeat.shape[1], col0, L.ptr(x), d, L.ptr(vec), B, Lm, L.ptr(dx), L.ptr(dvec), L.stream_ptr(x.device)),
+            'intel_op_gate_bwd')
+    return dx, dvec
+
+
+def gate_mean_fwd(x, vec, feat, col0):
+    B, Lm, d = x.shape
+    xbar = torch.empty_like(vec)
+    L.check(L.lib().intel_op_gate_mean_fwd(L.ptr(x), d, L.ptr(vec), B, Lm, L.ptr(xbar), L.ptr(feat), feat.shape[1], col0, L.stream_ptr(x.device)),
+            'intel_op_gate_mean_fwd')
+    return xbar, feat
+
+
+def gate_mean_bwd(dfeat, col0, xbar, vec, Lm):
+    B, d = vec.shape
+    dx, dvec = _f32((B, Lm, d), vec), torch.empty_like(vec)
+    L.check(L.lib().intel_op_gate_mean_bwd(L.ptr(dfeat), dfeat.shape[1], col0, L.ptr(xbar), d, L.ptr(vec), B, Lm, L.ptr(dx), L.ptr(dvec),
+                                           L.stream_ptr(vec.device)), 'intel_op_gate_mean_bwd')
+    return dx, dvec
+
+
+def session_colsum(src, col0, d, B, Lm, out, ocol0, accumulate=False):
+    L.check(L.lib().intel_op_session_colsum(L.ptr(src), src.shape[1], col0, d, B, Lm, L.ptr(out), out.shape[1], ocol0, int(accumulate),
+                                            L.stream_ptr(src.device)), 'intel_op_session_colsum')
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------
 # torch.library registration: the same entry points as dispatcher-visible custom ops, `torch.ops.intel_mi355x.*`
 # (north_star: "exposed ... as PyTorch-ROCm custom ops"; SURVEY.md 8-b(2)).  The C ABI stays the lowest layer; these are
 # thin schemas over it with shape ("fake") functions for tracing and autograd formulas where the reference differentiates
