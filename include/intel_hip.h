@@ -560,6 +560,29 @@ int intel_op_gate_mean_bwd(const float* dfeat, int ldf, int col0, const float* x
 int intel_op_session_colsum(const float* src, int lds, int col0, int d, int B, int L, float* out, int ldo, int ocol0, int accumulate,
                             void* stream);
 
+/* ---- GRU4Rec recurrence (exported for unit tests; see tests/test_gru_op_gpu.py) ------------
+ * The encoder of models/GeneralSeq.py:58-78 with hidden size 128: a one-layer GRU (gates r, z, n; h' = (1 - z) n + z h; h_0 = 0;
+ * a session keeps its state from step len[b] on) followed by the bias-free projection of the last state.  Both entries lay the
+ * encoder's buffers out over `workspace` (intel_op_gru_workspace_bytes, 256-byte aligned); the backward reads what a forward with
+ * stash != 0 left there, so it must follow one with the same shape, rows, order and form on the same workspace.
+ *   E0 [B*T, dm] padded history rows (row b*T + t), or, off != NULL, [rows, dm] packed rows: session b owns rows off[b] ..
+ *   off[b] + len[b] - 1 (off = exclusive prefix sum of len, rows = its total); order (or NULL): a permutation of the sessions,
+ *   workgroup slot i handles session order[i]; Wih [384, dm], Whh [384, 128], bih / bhh [384], Wout [dm, 128].
+ *   form: 0 hidden GEMM + gate kernel per step (padded rows only: INTEL_E_ARG with off), 1 one-kernel recurrence with exact fp32
+ *   MFMAs, 2 with three-plane bf16 products, -1 the process-wide INTEL_GRU_SEQ. */
+size_t intel_op_gru_workspace_bytes(int B, int T, int dm);
+/* out[b, col0:col0+dm] = h_last[b] Wout^T; the other columns of out [B, ldo] are not touched.  stash == 0 (inference, forms 1 / 2): no
+ * gate / state stash is kept. */
+int intel_op_gru_fwd(const float* E0, int B, int T, int dm, const int* len, const int* off, int rows, const int* order, const float* Wih,
+                     const float* Whh, const float* bih, const float* bhh, const float* Wout, float* out, int ldo, int col0, int stash, int form,
+                     void* workspace, size_t workspace_bytes, void* stream);
+/* Its backward under autograd from dvec = dout[b, col0:col0+dm]: every parameter gradient is overwritten; dE0 like E0 (padded: all
+ * T rows written, zeros from len[b] on; packed: the rows valid rows).  queued != 0: the weight gradients go through a reduction
+ * queue flushed before return, else through the immediate reduction. */
+int intel_op_gru_bwd(const float* E0, int B, int T, int dm, const int* len, const int* off, int rows, const int* order, const float* Whh,
+                     const float* bhh, const float* dout, int ldo, int col0, float* dWih, float* dWhh, float* dbih, float* dbhh, float* dWout,
+                     float* dE0, int queued, int form, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

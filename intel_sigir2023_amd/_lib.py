@@ -140,6 +140,8 @@ EXPORTS = [
     'intel_op_attn_lastq_fwd', 'intel_op_attn_lastq_bwd', 'intel_op_select_last', 'intel_op_add_at_last', 'intel_op_layernorm_bwd', 'intel_op_layernorm_bwd_workspace_bytes',
     'intel_op_softmax_rows', 'intel_op_softmax_rows_bwd', 'intel_op_scatter_add_rows', 'intel_op_scatter_add_sorted', 'intel_op_gate_fwd', 'intel_op_gate_bwd',
     'intel_op_gate_mean_fwd', 'intel_op_gate_mean_bwd', 'intel_op_session_colsum',
+    # GRU4Rec recurrence (tests/test_gru_op_gpu.py)
+    'intel_op_gru_workspace_bytes', 'intel_op_gru_fwd', 'intel_op_gru_bwd',
 ]
 
 
@@ -217,6 +219,9 @@ def _declare(l):
     sig('intel_op_gate_mean_fwd', i, [vp, i, vp, i, i, vp, vp, i, i, vp])
     sig('intel_op_gate_mean_bwd', i, [vp, i, i, vp, i, vp, i, i, vp, vp, vp])
     sig('intel_op_session_colsum', i, [vp, i, i, i, i, i, vp, i, i, i, vp])
+    sig('intel_op_gru_workspace_bytes', sz, [i, i, i])
+    sig('intel_op_gru_fwd', i, [vp, i, i, i, vp, vp, i, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, vp, sz, vp])
+    sig('intel_op_gru_bwd', i, [vp, i, i, i, vp, vp, i, vp, vp, vp, vp, i, i, vp, vp, vp, vp, vp, vp, i, i, vp, sz, vp])
     sig('intel_rows_take', i, [vp, i, vp, i, vp, i, vp])
     sig('intel_rows_add', i, [vp, i, vp, i, vp, vp])
     sig('intel_rows_compact', i, [vp, C.c_longlong, vp, i, vp, vp])

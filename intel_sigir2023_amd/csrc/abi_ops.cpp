@@ -442,3 +442,69 @@ extern "C" int intel_op_session_colsum(const float* src, int lds, int col0, int 
   INTEL_CHECK_ARG(src && out && d > 0 && col0 >= 0 && lds >= col0 + d && ocol0 >= 0 && ldo >= ocol0 + d, "op_session_colsum: bad argument");
   return launch_session_colsum(src, lds, col0, d, B, L, out, ldo, ocol0, accumulate, (hipStream_t)stream);
 }
+
+// ---- GRU4Rec recurrence (gru.hip): thin entries for the unit tests ----------------------------------------------------
+#include "gru.h"
+
+// workspace: packed weights | activations and backward temporaries of B*T rows | immediate weight-gradient slabs | reduce arena
+struct GruOpWs {
+  GruBufs g;
+  float *slabs, *arena;
+  size_t arena_floats, bytes;
+};
+static GruOpWs gru_op_layout(int B, int T, int dm, char* base) {
+  const int Hd = 128;
+  GruOpWs w;
+  size_t off = 0;
+  gru_layout_packed(w.g, dm, Hd, base, off);
+  gru_layout_act(w.g, B, T, dm, Hd, base, off);
+  const size_t s_ih = wgrad_slab_floats(B * T, 3 * Hd, dm), s_hh = wgrad_slab_floats(B * T, 3 * Hd, Hd), s_out = wgrad_slab_floats(B, dm, Hd);
+  const size_t smax = s_ih > s_hh ? (s_ih > s_out ? s_ih : s_out) : (s_hh > s_out ? s_hh : s_out);
+  off = rup_sz(off, 256);
+  w.slabs = reinterpret_cast<float*>(base + off);
+  off += smax * sizeof(float);
+  off = rup_sz(off, 256);
+  w.arena = reinterpret_cast<float*>(base + off);
+  w.arena_floats = rup_sz(s_ih, 64) + rup_sz(s_hh, 64) + rup_sz(s_out, 64);      // the queue keeps all three until its flush
+  off += op_arena_bytes(w.arena_floats);
+  w.bytes = off;
+  return w;
+}
+
+extern "C" size_t intel_op_gru_workspace_bytes(int B, int T, int dm) {
+  if (B <= 0 || T <= 0 || dm <= 0) return 0;
+  return gru_op_layout(B, T, dm, nullptr).bytes;
+}
+
+#define GRU_OP_CHECK(what)                                                                                                                \
+  INTEL_CHECK_ARG(B > 0 && T > 0 && dm > 0 && col0 >= 0 && ldo >= col0 + dm && form >= -1 && form <= 2, what ": bad shape or form");        \
+  INTEL_CHECK_ARG(!off || rows > 0, what ": packed history rows need rows > 0");                                                          \
+  INTEL_CHECK_ARG(!off || (form < 0 ? gru_packed_supported(128) : form != 0), what ": packed history rows need the one-kernel recurrence"); \
+  INTEL_CHECK_ARG(workspace && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0 && workspace_bytes >= intel_op_gru_workspace_bytes(B, T, dm), \
+                  what ": workspace missing, not 256-byte aligned or too small")
+
+extern "C" int intel_op_gru_fwd(const float* E0, int B, int T, int dm, const int* len, const int* off, int rows, const int* order, const float* Wih,
+                                const float* Whh, const float* bih, const float* bhh, const float* Wout, float* out, int ldo, int col0, int stash,
+                                int form, void* workspace, size_t workspace_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  INTEL_CHECK_ARG(E0 && len && Wih && Whh && bih && bhh && Wout && out, "op_gru_fwd: null argument");
+  GRU_OP_CHECK("op_gru_fwd");
+  GruOpWs w = gru_op_layout(B, T, dm, (char*)workspace);
+  int rc = gru_pack(w.g, Wih, Whh, Wout, dm, 128, st);
+  if (rc) return rc;
+  return gru_fwd(w.g, E0, B, T, dm, 128, len, bih, bhh, out, ldo, col0, st, Whh, off, rows, order, stash != 0, form);
+}
+
+extern "C" int intel_op_gru_bwd(const float* E0, int B, int T, int dm, const int* len, const int* off, int rows, const int* order, const float* Whh,
+                                const float* bhh, const float* dout, int ldo, int col0, float* dWih, float* dWhh, float* dbih, float* dbhh,
+                                float* dWout, float* dE0, int queued, int form, void* workspace, size_t workspace_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  INTEL_CHECK_ARG(E0 && len && Whh && bhh && dout && dWih && dWhh && dbih && dbhh && dWout && dE0, "op_gru_bwd: null argument");
+  GRU_OP_CHECK("op_gru_bwd");
+  GruOpWs w = gru_op_layout(B, T, dm, (char*)workspace);
+  const GruGrads gg = {dWih, dWhh, dbih, dbhh, dWout};
+  if (!queued) return gru_bwd(w.g, E0, B, T, dm, 128, len, Whh, bhh, dout, ldo, col0, gg, dE0, nullptr, w.slabs, st, off, rows, order, nullptr, form);
+  return with_queue(w.arena, op_arena_bytes(w.arena_floats), w.arena_floats, st, "op_gru_bwd", [&](ReduceQueue* q) {
+    return gru_bwd(w.g, E0, B, T, dm, 128, len, Whh, bhh, dout, ldo, col0, gg, dE0, nullptr, nullptr, st, off, rows, order, q, form);
+  });
+}

@@ -25,10 +25,12 @@ int gru_fwd(GruBufs& g, const float* E0, int B, int T, int dm, int Hd, const int
             float* out, int ldo, int col0, hipStream_t st, const float* Whh = nullptr,       // Whh (raw [3H, H]): the one-kernel recurrence
             const int* off = nullptr, int rows = 0,      // off / rows: E0 holds only the valid history rows (session b: rows off[b] .. off[b] + len[b])
             const int* order = nullptr,                  // sessions ordered by length (IntelBatch.his_order)
-            bool stash = true);                          // false (inference): the recurrence keeps no gate / state stash
+            bool stash = true,                           // false (inference): the recurrence keeps no gate / state stash
+            int form = -1);                              // the recurrence form of THIS call (0 / 1 / 2 as INTEL_GRU_SEQ; -1: the process-wide switch)
 bool gru_packed_supported(int Hd);
 // dvec = dout[b, col0:col0+dm]; writes parameter grads (overwrite) and dE0 [B*T, dm]
 int gru_bwd(GruBufs& g, const float* E0, int B, int T, int dm, int Hd, const int* len, const float* Whh, const float* bhh,
             const float* dout, int ldo, int col0, const GruGrads& gg, float* dE0, float* scratch, float* slabs,
             hipStream_t st, const int* off = nullptr, int rows = 0, const int* order = nullptr,
-            struct ReduceQueue* q = nullptr);      // q: the weight gradients' slabs join the backward's batched reduction instead of three immediate ones
+            struct ReduceQueue* q = nullptr,       // q: the weight gradients' slabs join the backward's batched reduction instead of three immediate ones
+            int form = -1);                        // as gru_fwd's; must be the form of the forward that filled the stash

@@ -728,23 +728,25 @@ static int gru_seq_mode() {
   static const int m = [] { const char* e = getenv("INTEL_GRU_SEQ"); return e ? atoi(e) : 2; }();
   return m;
 }
-static bool gru_seq_on(int Hd, const float* Whh) {
-  return gru_seq_mode() != 0 && Hd == GS_H && Whh != nullptr && (reinterpret_cast<uintptr_t>(Whh) & 15) == 0;
+// mode: the form of one call (gru_fwd / gru_bwd's `form`, -1 = the process-wide switch)
+static bool gru_seq_on(int Hd, const float* Whh, int mode) {
+  return mode != 0 && Hd == GS_H && Whh != nullptr && (reinterpret_cast<uintptr_t>(Whh) & 15) == 0;
 }
 
 bool gru_packed_supported(int Hd) { return gru_seq_mode() != 0 && Hd == GS_H; }
 bool gru_ext_proj_supported(int dm, int Hd) { return gru_seq_mode() != 0 && Hd == GS_H && dm % 16 == 0; }
 
 int gru_fwd(GruBufs& g, const float* E0, int B, int T, int dm, int Hd, const int* len, const float* bih, const float* bhh,
-            float* out, int ldo, int col0, hipStream_t st, const float* Whh, const int* off, int rows, const int* order, bool stash) {
+            float* out, int ldo, int col0, hipStream_t st, const float* Whh, const int* off, int rows, const int* order, bool stash, int form) {
+  const int mode = form >= 0 ? form : gru_seq_mode();
   if (!off) rows = B * T;
-  INTEL_CHECK_ARG(!off || gru_seq_on(Hd, Whh), "gru: packed history rows need the one-kernel recurrence (hidden size 128, aligned W_hh)");
-  if (gru_seq_on(Hd, Whh)) {
+  INTEL_CHECK_ARG(!off || gru_seq_on(Hd, Whh, mode), "gru: packed history rows need the one-kernel recurrence (hidden size 128, aligned W_hh)");
+  if (gru_seq_on(Hd, Whh, mode)) {
     int rc;
     GemmEpilogue ei;
     ei.bias = bih;
     if ((rc = launch_gemm_rows(E0, dm, rows, dm, g.pWih, 3 * Hd, g.GI, 3 * Hd, ei, st))) return rc;
-    if (gru_seq_mode() == 1)
+    if (mode == 1)
       LAUNCH(gru_seq_fwd_kernel<false>, dim3(cdiv(B, GS_ROWS)), dim3(512), 0, st, g.GI, Whh, bhh, len, B, T, g.HP, g.HCUR, g.GATES, g.GHN, off, order);
     else if (stash)
       LAUNCH(gru_seq_fwd_kernel<true>, dim3(cdiv(B, GS_ROWS)), dim3(512), 0, st, g.GI, Whh, bhh, len, B, T, g.HP, g.HCUR, g.GATES, g.GHN, off, order);
@@ -797,18 +799,19 @@ int gru_fwd_steps(GruBufs& g, const float* E0, int B, int T, int dm, int Hd, con
 
 int gru_bwd(GruBufs& g, const float* E0, int B, int T, int dm, int Hd, const int* len, const float* Whh, const float* bhh,
             const float* dout, int ldo, int col0, const GruGrads& gg, float* dE0, float* scratch, float* slabs,
-            hipStream_t st, const int* off, int prows, const int* order, ReduceQueue* q) {
+            hipStream_t st, const int* off, int prows, const int* order, ReduceQueue* q, int form) {
   (void)bhh; (void)scratch;
-  INTEL_CHECK_ARG(!off || gru_seq_on(Hd, Whh), "gru: packed history rows need the one-kernel recurrence (hidden size 128, aligned W_hh)");
+  const int mode = form >= 0 ? form : gru_seq_mode();
+  INTEL_CHECK_ARG(!off || gru_seq_on(Hd, Whh, mode), "gru: packed history rows need the one-kernel recurrence (hidden size 128, aligned W_hh)");
   int rc;
   // vec = HCUR Wout^T
   if (!g.ext_proj && gg.dWout && (rc = launch_wgrad(dout + col0, ldo, g.HCUR, Hd, B, dm, Hd, gg.dWout, Hd, nullptr, 0, slabs, st, q))) return rc;
   GemmEpilogue e0;
   float *dH = g.dHa, *dHn = g.dHb;
   if (!g.ext_proj && (rc = launch_gemm_rows(dout + col0, ldo, B, dm, g.pWoutT, Hd, dH, Hd, e0, st))) return rc;
-  const bool seq = gru_seq_on(Hd, Whh);
+  const bool seq = gru_seq_on(Hd, Whh, mode);
   if (seq) {
-    if (gru_seq_mode() == 1)
+    if (mode == 1)
       LAUNCH(gru_seq_bwd_kernel<false>, dim3(cdiv(B, GS_ROWS)), dim3(512), 0, st, dH, g.HP, g.GATES, g.GHN, Whh, len, B, T, g.dGI, g.dGH, off, order);
     else
       LAUNCH(gru_seq_bwd_kernel<true>, dim3(cdiv(B, GS_ROWS)), dim3(512), 0, st, dH, g.HP, g.GATES, g.GHN, Whh, len, B, T, g.dGI, g.dGH, off, order);

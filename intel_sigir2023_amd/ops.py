@@ -274,6 +274,36 @@ def session_colsum(src, col0, d, B, Lm, out, ocol0, accumulate=False):
 
 
 # ------------------------------------------------------------------------------------------------------------------------
+# GRU4Rec recurrence (csrc/gru.hip) for the unit tests (tests/test_gru_op_gpu.py).  ctypes only.  The caller owns the workspace:
+# the backward reads the stash that the forward left in it.
+# ------------------------------------------------------------------------------------------------------------------------
+def gru_workspace(B, T, dm, device):
+    return _ws(L.lib().intel_op_gru_workspace_bytes(B, T, dm), device)
+
+
+def gru_fwd(E0, B, T, length, Wih, Whh, bih, bhh, Wout, out, col0, ws, form=-1, stash=True, off=None, order=None):
+    """E0 [B*T, dm] padded rows, or with off (int32 [B], exclusive prefix sum of length) the packed valid rows; hidden size 128.
+    out[:, col0:col0+dm] = h_last Wout^T is written in place.  form: 0 per step, 1 exact-fp32 recurrence, 2 three-plane recurrence."""
+    dm = E0.shape[1]
+    L.check(L.lib().intel_op_gru_fwd(L.ptr(E0), B, T, dm, L.ptr(length), L.ptr(off), E0.shape[0], L.ptr(order), L.ptr(Wih), L.ptr(Whh), L.ptr(bih),
+                                     L.ptr(bhh), L.ptr(Wout), L.ptr(out), out.shape[1], col0, int(stash), form, L.ptr(ws), ws.numel(),
+                                     L.stream_ptr(E0.device)), 'intel_op_gru_fwd')
+    return out
+
+
+def gru_bwd(E0, B, T, length, Whh, bhh, dout, col0, ws, form=-1, queued=False, off=None, order=None):
+    """After gru_fwd(..., stash=True) with the same arguments on the same workspace: dvec = dout[:, col0:col0+dm] ->
+    dict of dE0 (like E0), dWih, dWhh, dbih, dbhh, dWout."""
+    dm = E0.shape[1]
+    g = {'dE0': torch.empty_like(E0), 'dWih': _f32((384, dm), E0), 'dWhh': _f32((384, 128), E0), 'dbih': _f32((384,), E0), 'dbhh': _f32((384,), E0),
+         'dWout': _f32((dm, 128), E0)}
+    L.check(L.lib().intel_op_gru_bwd(L.ptr(E0), B, T, dm, L.ptr(length), L.ptr(off), E0.shape[0], L.ptr(order), L.ptr(Whh), L.ptr(bhh), L.ptr(dout),
+                                     dout.shape[1], col0, L.ptr(g['dWih']), L.ptr(g['dWhh']), L.ptr(g['dbih']), L.ptr(g['dbhh']), L.ptr(g['dWout']),
+                                     L.ptr(g['dE0']), int(queued), form, L.ptr(ws), ws.numel(), L.stream_ptr(E0.device)), 'intel_op_gru_bwd')
+    return g
+
+
+# ------------------------------------------------------------------------------------------------------------------------
 # torch.library registration: the same entry points as dispatcher-visible custom ops, `torch.ops.intel_mi355x.*`
 # (north_star: "exposed ... as PyTorch-ROCm custom ops"; SURVEY.md 8-b(2)).  The C ABI stays the lowest layer; these are
 # thin schemas over it with shape ("fake") functions for tracing and autograd formulas where the reference differentiates

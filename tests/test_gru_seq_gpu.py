@@ -4,7 +4,8 @@ process, so the same suites are re-run in child processes with the exact-fp32-MF
 form (0: hidden GEMM + gate kernel per step, the round-1 path): forward outputs, losses and every parameter gradient against
 the reference fixtures (gru_bpr: models/GeneralSeq.py:58-78 through torch.nn.GRU) and the oracle's autograd, unchanged
 tolerances.  A direct comparison of the three forms on one batch with ragged histories (lengths 0 .. T, a batch that is not a
-multiple of the 16-session workgroup tile) follows."""
+multiple of the 16-session workgroup tile) follows.  The comparison of each form with an independent float64 GRU, at the shapes
+where the kernels branch, lives in tests/test_gru_op_gpu.py."""
 import os
 import subprocess
 import sys
