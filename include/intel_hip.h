@@ -378,6 +378,30 @@ int intel_eval_metrics(int B, int L, int width, int n_topk, const int* topk, con
                        const int* session_len, const int* pos_nums, const int* label_pos, double* out, unsigned char* valid,
                        void* stream);
 
+/* ---- ERA baseline (Evolutionary Rank Aggregation) ------------------------------------------------
+ * The comparison method of models/supervise/ERA.py + ERARunner.py: a genetic algorithm over the weights of a tiny MLP on rank
+ * features.  The reference scores one solution at a time (pygad.torchga.predict + the numpy evaluate_method, ERARunner.py:138-148);
+ * intel_era_fitness scores a whole population per launch. */
+/* ERA.Dataset._get_feed_dict (models/supervise/ERA.py:54-65): feat [B, L, 2 + K] = [p10, mAgr, psc_0 .. psc_{K-1}] per item, all
+ * zero from session_len on.  rank_m(l) = 1 + #{j < len : s_m(j) > s_m(l) or (s_m(j) == s_m(l) and j > l)} (np.argsort(x)[::-1],
+ * stable: among equal scores the later slot ranks better); psc_m = float32 of the float64 1 - (rank_m - 1) / len; p10 = #{m : rank_m
+ * <= 10}; mAgr = 0.5 * [|rank_1 - rank_0| <= window].  scores [B, L, K] fp32, 2 <= K <= 6, L <= 256. */
+int intel_era_features(int B, int L, int K, const float* scores, const int* session_len, int window, float* feat, void* stream);
+/* Fitness of P solutions on a batch (ERARunner.py:138-148: fitness_func = NDCG@1 of evaluate_method, :87-97, over ERA.forward,
+ * ERA.py:39-45).  pop [P, G]: one fp32 weight vector per solution in pygad.torchga's layout, the state_dict order of ERA.mlp
+ * (ERA.py:31-37): per Linear weight [out, in] row-major then bias [out]; n_hidden Linear + ReLU layers of the HOST widths `hidden`,
+ * then a Linear with out = 1.  pred[p, b, l] = mlp_p(feat[b, l, :]) for l < session_len; the session's winner is the largest
+ * prediction among its items (label max(ranking, 0)) and, when session_len < width, one pad candidate of prediction 0 / label 0
+ * (:45-57) -- among equal predictions the smallest label; gain = label_winner / max(1, largest label of the session) (idcg == 0 -> 1,
+ * :95).  gain_sum[p] += sum_b gain[p, b] (double [P], accumulated, never reset: chain the batches of an evaluation set and divide by
+ * the session count once); the sum is bit-reproducible (per-workgroup partials in `workspace`, intel_era_fitness_workspace_bytes
+ * bytes, then a fixed-order pass).  pred_out (or NULL): pred [P, B, L], pad slots 0.
+ * Limits (INTEL_E_ARG otherwise): L <= 256, 4 <= F <= 8, 1 <= n_hidden <= 2, hidden widths <= 64, P >= 1. */
+size_t intel_era_fitness_workspace_bytes(int P, int B);
+int intel_era_fitness(int P, int B, int L, int F, int n_hidden, const int* hidden, const float* pop, const float* feat,
+                      const int* ranking, const int* session_len, int width, double* gain_sum, float* pred_out, void* workspace,
+                      void* stream);
+
 /* ---- input feed ------------------------------------------------------------------------------ */
 /* Device-side batch assembly: the work of the reference's per-sample Dataset._get_feed_dict chain
  * (models/BaseModel.py:158-197, models/GeneralSeq.py:35-54, models/IntEL/IntEL.py:220-239) and of

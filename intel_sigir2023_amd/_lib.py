@@ -142,6 +142,8 @@ EXPORTS = [
     'intel_op_gate_mean_fwd', 'intel_op_gate_mean_bwd', 'intel_op_session_colsum',
     # GRU4Rec recurrence (tests/test_gru_op_gpu.py)
     'intel_op_gru_workspace_bytes', 'intel_op_gru_fwd', 'intel_op_gru_bwd',
+    # ERA baseline (era.py)
+    'intel_era_features', 'intel_era_fitness_workspace_bytes', 'intel_era_fitness',
 ]
 
 
@@ -222,6 +224,9 @@ def _declare(l):
     sig('intel_op_gru_workspace_bytes', sz, [i, i, i])
     sig('intel_op_gru_fwd', i, [vp, i, i, i, vp, vp, i, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, vp, sz, vp])
     sig('intel_op_gru_bwd', i, [vp, i, i, i, vp, vp, i, vp, vp, vp, vp, i, i, vp, vp, vp, vp, vp, vp, i, i, vp, sz, vp])
+    sig('intel_era_features', i, [i, i, i, vp, vp, i, vp, vp])
+    sig('intel_era_fitness_workspace_bytes', sz, [i, i])
+    sig('intel_era_fitness', i, [i, i, i, i, i, C.POINTER(C.c_int), vp, vp, vp, vp, i, vp, vp, vp, vp])
     sig('intel_rows_take', i, [vp, i, vp, i, vp, i, vp])
     sig('intel_rows_add', i, [vp, i, vp, i, vp, vp])
     sig('intel_rows_compact', i, [vp, C.c_longlong, vp, i, vp, vp])

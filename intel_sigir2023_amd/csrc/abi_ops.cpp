@@ -4,6 +4,7 @@
 
 #include "../../include/intel_hip.h"
 #include "kernels.h"
+#include "era.h"
 
 static thread_local char g_err[512] = "";
 
@@ -507,4 +508,19 @@ extern "C" int intel_op_gru_bwd(const float* E0, int B, int T, int dm, const int
   return with_queue(w.arena, op_arena_bytes(w.arena_floats), w.arena_floats, st, "op_gru_bwd", [&](ReduceQueue* q) {
     return gru_bwd(w.g, E0, B, T, dm, 128, len, Whh, bhh, dout, ldo, col0, gg, dE0, nullptr, nullptr, st, off, rows, order, q, form);
   });
+}
+
+// ---- ERA baseline (era.hip) ---------------------------------------------------------------------------------------------
+extern "C" int intel_era_features(int B, int L, int K, const float* scores, const int* session_len, int window, float* feat, void* stream) {
+  INTEL_CHECK_ARG(scores && session_len && feat, "era_features: null tensor");
+  return launch_era_features(B, L, K, scores, session_len, window, feat, (hipStream_t)stream);
+}
+
+extern "C" size_t intel_era_fitness_workspace_bytes(int P, int B) { return era_fitness_ws_bytes(P, B); }
+
+extern "C" int intel_era_fitness(int P, int B, int L, int F, int n_hidden, const int* hidden, const float* pop, const float* feat,
+                                 const int* ranking, const int* session_len, int width, double* gain_sum, float* pred_out, void* workspace,
+                                 void* stream) {
+  INTEL_CHECK_ARG(pop && feat && ranking && session_len && gain_sum && workspace, "era_fitness: null tensor / workspace");
+  return launch_era_fitness(P, B, L, F, n_hidden, hidden, pop, feat, ranking, session_len, width, gain_sum, pred_out, workspace, (hipStream_t)stream);
 }

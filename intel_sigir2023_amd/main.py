@@ -20,12 +20,13 @@ from . import data as data_mod
 from . import feed
 from . import parallel
 from . import synth
+from .era import ERA, ERARunner
 from .model import IntEL, aWELv_IntEL
 from .runner import BaseRunner
 
-MODELS = {'IntEL': IntEL, 'aWELv_IntEL': aWELv_IntEL}
+MODELS = {'IntEL': IntEL, 'aWELv_IntEL': aWELv_IntEL, 'ERA': ERA}
 LOSSES = {n: getattr(loss_mod, n) for n in ('BPRloss', 'Listloss', 'MSEloss', 'IntBPRloss', 'IntListloss', 'IntMSEloss')}
-RUNNERS = {'BaseRunner': BaseRunner}
+RUNNERS = {'BaseRunner': BaseRunner, 'ERARunner': ERARunner}
 
 
 def parse_global_args(parser):
