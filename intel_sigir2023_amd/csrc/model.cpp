@@ -1900,8 +1900,11 @@ void forward_impl(Run& r, const IntelOut* out) {
 }
 
 // ---- backward -----------------------------------------------------------------------------------
+// the vectorised sorted scatter (launch_scatter_add_sorted) takes embedding widths that are a power of two from 16 to 128
+static bool sorted_scatter_ok(int d) { return d % 16 == 0 && d <= 128 && (d & (d - 1)) == 0; }
+
 // phase 0 = whole backward; phase 1 = everything the item-id table gradient depends on (so that its
-// data-parallel all-reduce can start) ; phase 2 = the rest (score tower layers, session-history encoder)
+// data-parallel all-reduce can start) and both sequence encoders; phase 2 = the rest (score tower layers)
 void backward_impl(Run& r, const float* d_weights, const float* d_ens, const float* d_intents, int phase) {
   const IntelDesc& D = r.D;
   Layout& y = r.y;
@@ -1990,52 +1993,8 @@ void backward_impl(Run& r, const float* d_weights, const float* d_ens, const flo
     if (r.rc) return;
   }
 
-  // ===== cross attention backward of one tower (cheap: B-row GEMMs + one pass over [B,L,d]); leaves the
-  // gradient w.r.t. the tower output in dXout and this tower's contribution to d(intent) in dint
-  auto xatt_bwd = [&](Run& r, int t, float* dXout, float* dint) {
-    TowerBufs& w = y.tw[t];
-    const int d = w.d;
-    const float* Xf = D.layers > 0 ? w.layer[D.layers - 1].Xout : w.X0;
-    float *g1 = y.dHB[t][0], *g2 = y.dHB[t][1], *g3 = y.dHB[t][2];      // B-row gradients (kept for the deferred weight gradients)
-    if (D.cross_attention) {
-      const int xb = w.xbase;
-      // pooled = xbar Wv^T
-      leaf(r, [=, &y, &w](Run& r) { wgrad(r, y.dFEAT + w.feat_off, y.F, w.XBAR, d, B, d, d, xb + 2, -1); });
-      lin(r, y.dFEAT + w.feat_off, y.F, B, d, w.pXvT, d, g1, d, e0);          // dxbar
-      if (r.rc) return;
-      if (r.ctx->fused_tail[t]) {       // dXout receives dZ: the gradient BEHIND the last layer's LayerNorm
-        const int pb = w.pbase;
-        TowerLayerBufs& lb = w.layer[D.layers - 1];
-        const int a = r.acc(pb + T_LNG);
-        r.acc(pb + T_LNB);
-        RUN(launch_xatt_pool_ln_bwd(lb.XH, lb.RSTD, r.P(pb + T_LNG), r.P(pb + T_LNB), B, L, d, w.QK, w.ATTW, g1, d, scale, dXout,
-                                    g2, r.G(pb + T_LNG), r.G(pb + T_LNB), a, r.st, r.ctx->rq));
-      } else {
-        RUN(launch_xatt_pool_bwd(Xf, B, L, d, w.QK, w.ATTW, g1, d, scale, dXout, g2, r.st));   // dX, dQK
-      }
-      // QK = QV Wk  (QK[b][j] = sum_i QV[b][i] Wk[i][j])
-      leaf(r, [=, &w](Run& r) { wgrad(r, w.QV, d, g2, d, B, d, d, xb + 1, -1); });
-      lin(r, g2, d, B, d, w.pXk, d, g3, d, e0);                            // dQV
-      leaf(r, [=, &y](Run& r) { wgrad(r, g3, d, y.INTENTS, I, B, d, I, xb + 0, -1); });
-      lin(r, g3, d, B, d, w.pXqT, I, dint, I, e0);
-    } else {
-      const int mb = t == 0 ? INTEL_P_MI_W0 : INTEL_P_MS_W0;
-      if (D.pool_mean)
-        RUN(launch_gate_mean_bwd(y.dFEAT, y.F, w.feat_off, w.XBAR, d, w.MV, B, L, dXout, g1, r.st));   // dX (every row), dMV
-      else
-        RUN(launch_gate_bwd(y.dFEATFULL, y.F, w.feat_off, Xf, d, w.MV, B, L, dXout, g1, r.st));    // dX, dMV
-      const int qs = D.q_size;
-      leaf(r, [=, &w](Run& r) { wgrad(r, g1, d, w.MH, qs, B, d, qs, mb + 2, -1); });
-      GemmEpilogue em;
-      em.mask = w.MH; em.ldmask = D.q_size;
-      lin(r, g1, d, B, d, w.pM2T, D.q_size, g2, D.q_size, em);            // d(pre-relu hidden)
-      leaf(r, [=, &y](Run& r) { wgrad(r, g2, qs, y.INTENTS, I, B, qs, I, mb + 0, mb + 1); });
-      lin(r, g2, D.q_size, B, D.q_size, w.pM0T, I, dint, I, e0);
-    }
-  };
-  // the same with the chain launches around it (hfused): only the pooling kernel; dxbar (g1) comes from head_bwd_a, dQV (g3), the
-  // share of d(intent) and the three projections' weight gradients from the chains
-  auto pool_bwd_fused = [&](Run& r, int t, float* dXout) {
+  // ===== backward of one tower's cross-attention pooling: dxbar (dHB[t][0]) -> the gradient w.r.t. the tower output in dXout, dQK in dHB[t][1]
+  auto pool_bwd = [&](Run& r, int t, float* dXout) {
     TowerBufs& w = y.tw[t];
     const int d = w.d;
     float *g1 = y.dHB[t][0], *g2 = y.dHB[t][1];
@@ -2050,26 +2009,80 @@ void backward_impl(Run& r, const float* d_weights, const float* d_ens, const flo
       RUN(launch_xatt_pool_bwd(D.layers > 0 ? w.layer[D.layers - 1].Xout : w.X0, B, L, d, w.QK, w.ATTW, g1, d, scale, dXout, g2, r.st));
     }
   };
+  // ===== cross attention backward of one tower (cheap: B-row GEMMs + one pass over [B,L,d]); leaves the
+  // gradient w.r.t. the tower output in dXout and this tower's contribution to d(intent) in dint.  (The chain schedule runs
+  // pool_bwd alone: dxbar comes from head_bwd_a, dQV, the share of d(intent) and the three projections' weight gradients from the chains.)
+  auto xatt_bwd = [&](Run& r, int t, float* dXout, float* dint) {
+    TowerBufs& w = y.tw[t];
+    const int d = w.d;
+    float *g1 = y.dHB[t][0], *g2 = y.dHB[t][1], *g3 = y.dHB[t][2];      // B-row gradients (kept for the deferred weight gradients)
+    if (D.cross_attention) {
+      const int xb = w.xbase;
+      // pooled = xbar Wv^T
+      leaf(r, [=, &y, &w](Run& r) { wgrad(r, y.dFEAT + w.feat_off, y.F, w.XBAR, d, B, d, d, xb + 2, -1); });
+      lin(r, y.dFEAT + w.feat_off, y.F, B, d, w.pXvT, d, g1, d, e0);          // dxbar
+      if (r.rc) return;
+      pool_bwd(r, t, dXout);                                                  // dX, dQK
+      if (r.rc) return;
+      // QK = QV Wk  (QK[b][j] = sum_i QV[b][i] Wk[i][j])
+      leaf(r, [=, &w](Run& r) { wgrad(r, w.QV, d, g2, d, B, d, d, xb + 1, -1); });
+      lin(r, g2, d, B, d, w.pXk, d, g3, d, e0);                            // dQV
+      leaf(r, [=, &y](Run& r) { wgrad(r, g3, d, y.INTENTS, I, B, d, I, xb + 0, -1); });
+      lin(r, g3, d, B, d, w.pXqT, I, dint, I, e0);
+    } else {
+      const int mb = t == 0 ? INTEL_P_MI_W0 : INTEL_P_MS_W0;
+      if (D.pool_mean)
+        RUN(launch_gate_mean_bwd(y.dFEAT, y.F, w.feat_off, w.XBAR, d, w.MV, B, L, dXout, g1, r.st));   // dX (every row), dMV
+      else
+        RUN(launch_gate_bwd(y.dFEATFULL, y.F, w.feat_off, D.layers > 0 ? w.layer[D.layers - 1].Xout : w.X0, d, w.MV, B, L, dXout, g1, r.st));    // dX, dMV
+      const int qs = D.q_size;
+      leaf(r, [=, &w](Run& r) { wgrad(r, g1, d, w.MH, qs, B, d, qs, mb + 2, -1); });
+      GemmEpilogue em;
+      em.mask = w.MH; em.ldmask = D.q_size;
+      lin(r, g1, d, B, d, w.pM2T, D.q_size, g2, D.q_size, em);            // d(pre-relu hidden)
+      leaf(r, [=, &y](Run& r) { wgrad(r, g2, qs, y.INTENTS, I, B, qs, I, mb + 0, mb + 1); });
+      lin(r, g2, D.q_size, B, D.q_size, w.pM0T, I, dint, I, e0);
+    }
+  };
   // ===== tied self-attention layers of the item tower + its embedding-table gradients
   auto item_tower_bwd = [&](Run& r, float* dXout) {
     TowerBufs& w = y.tw[0];
     const int d = w.d;
     float* dX0 = tower_bwd(r, w, dXout, dXout == r.T->dXa ? r.T->dXb : r.T->dXa, r.ctx->fused_tail[0]);
     if (r.rc || !dX0) return;
-    const bool vec = (D.d_id % 16 == 0) && D.d_id <= 128 && (D.d_id & (D.d_id - 1)) == 0;
-    const bool vecm = (D.d_im % 16 == 0) && D.d_im <= 128 && (D.d_im & (D.d_im - 1)) == 0;
     if (r.G(INTEL_P_IID_EMB)) {
-      if (bt.iid_sort_ids && bt.iid_sort_rows && vec)
+      if (bt.iid_sort_ids && bt.iid_sort_rows && sorted_scatter_ok(D.d_id))
         RUN(launch_scatter_add_sorted(dX0, d, 0, D.d_id, bt.iid_sort_ids, bt.iid_sort_rows, M, r.G(INTEL_P_IID_EMB), r.st, r.ctx->iid_row_flags));
       else
         RUN(launch_scatter_add_rows(dX0, d, 0, D.d_id, bt.i_id_s, M, r.G(INTEL_P_IID_EMB), nullptr, 0, 0, r.st, r.ctx->iid_row_flags));
     }
     if (D.d_im > 0 && r.G(INTEL_P_ITEM_EMB)) {
-      if (bt.cls_sort_ids && bt.cls_sort_rows && vecm)
+      if (bt.cls_sort_ids && bt.cls_sort_rows && sorted_scatter_ok(D.d_im))
         RUN(launch_scatter_add_sorted(dX0, d, D.d_id, D.d_im, bt.cls_sort_ids, bt.cls_sort_rows, M, r.G(INTEL_P_ITEM_EMB), r.st));
       else
         RUN(launch_scatter_add_rows(dX0, d, D.d_id, D.d_im, bt.i_class_c, M, r.G(INTEL_P_ITEM_EMB), nullptr, 0, 0, r.st));
     }
+  };
+  // ===== tied self-attention layers of the score tower (its output gradient is in dXS; tower_bwd ping-pongs dXS <-> the set's dXb)
+  // + the score-embedding weight gradient
+  auto score_tower_bwd = [&](Run& r) {
+    float* dX0 = tower_bwd(r, ts, y.dXS, r.T->dXb, r.ctx->fused_tail[1]);
+    if (!r.rc && dX0) wgrad(r, dX0, ts.d, bt.scores, K, M, ts.d, K, INTEL_P_SCORE_W, INTEL_P_SCORE_B);
+  };
+  // ===== d(intent) = the head's share (dINTENT) + both towers' + the caller's, then the softmax backward: dLOGITS (kernel-per-op head)
+  auto dintent_chain = [&](Run& r, const float* d_intents) {
+    RUN(launch_add2(y.dINTENT, y.tmp[0].dINT, (long long)B * I, y.dINTENT, r.st));
+    RUN(launch_add2(y.dINTENT, y.tmp[1].dINT, (long long)B * I, y.dINTENT, r.st));
+    if (d_intents) RUN(launch_add2(y.dINTENT, d_intents, (long long)B * I, y.dINTENT, r.st));
+    RUN(launch_softmax_rows_bwd(y.INTENTS, y.dINTENT, B, I, y.dLOGITS, r.st));
+  };
+  // ===== context / user table gradients from d(pred_layer input)
+  auto predin_scatters = [&](Run& r) {
+    if (r.rc) return;
+    if (r.G(INTEL_P_CTX_EMB))
+      RUN(launch_scatter_add_rows(y.dPREDIN, y.Pin, 0, D.d_c, bt.context_mh, B, r.G(INTEL_P_CTX_EMB), nullptr, 0, 0, r.st));
+    if (r.G(INTEL_P_UID_EMB))
+      RUN(launch_scatter_add_rows(y.dPREDIN, y.Pin, D.d_c, D.d_u, bt.u_id_c, B, r.G(INTEL_P_UID_EMB), nullptr, 0, 0, r.st));
   };
   // ===== one sequence encoder: returns dE (gradient w.r.t. its input rows), scatters the table part
   auto encoder_branch = [&](Run& r, int e) -> float* {
@@ -2095,9 +2108,8 @@ void backward_impl(Run& r, const float* d_weights, const float* d_ens, const flo
       if (r.G(INTEL_P_CTX_EMB))
         r.ok(launch_scatter_add_rows(dE, dm, 0, D.d_c, pk ? n.pkIds : bt.his_context_mh, rows, r.G(INTEL_P_CTX_EMB), nullptr, 0, 0, r.st));
     } else {
-      const bool vec = (D.d_id % 16 == 0) && D.d_id <= 128 && (D.d_id & (D.d_id - 1)) == 0;
       if (r.G(INTEL_P_IID_EMB)) {
-        if (bt.hisitem_sort_ids && bt.hisitem_sort_rows && vec)
+        if (bt.hisitem_sort_ids && bt.hisitem_sort_rows && sorted_scatter_ok(D.d_id))
           r.ok(launch_scatter_add_sorted(dE, dm, 0, D.d_id, bt.hisitem_sort_ids, bt.hisitem_sort_rows, B * n.T, r.G(INTEL_P_IID_EMB), r.st,
                                          r.ctx->iid_row_flags, pk ? bt.hisitem_off : nullptr, bt.history_item_len, n.T));
         else
@@ -2123,36 +2135,58 @@ void backward_impl(Run& r, const float* d_weights, const float* d_ens, const flo
     }
   };
 
-  // ===== the whole backward in one call (phase 0) with the branches on four streams: nothing heavy waits for a chain of small
-  // launches it does not depend on.
-  //   side 2:  cross-attention backward of the score tower -> [x1] -> score tower layers (set 3) -> wait c -> the head's leaves
-  //   main:    cross-attention backward of the item tower -> [x0] -> wait x1 -> d(intent) chain -> [c] -> item-history encoder (set 1)
-  //   side 1:  wait x0 -> item tower layers + item-id / class table gradients (set 0)
-  //   side 0:  wait c -> session-history encoder (set 2)
-  //   main:    join; [iid] (the caller's table stream waits for it: intel_set_table_stream); shared intent-embedding gradients, reductions
-  // The two-call form (phases 1 and 2) keeps its order: there the caller overlaps the table's all-reduce with phase 2.
-  if (wide && hfused) {
-    // The same four branches with the session head as chain launches.  The d(intent) chain (head_bwd_b) is the critical link -- both
-    // encoders wait for it -- and it is a SMALL launch (B / 16 workgroups) that must not queue behind the towers' kernels for LDS:
-    //   main:    [head_bwd_a above] -> pooling backward of the item tower -> [x0] -> wait x1 -> head_bwd_b -> [c] -> item-history encoder
-    //   side 2:  pooling backward of the score tower -> [x1] -> wait c -> score tower (set 3) -> the head's table scatters
-    //   side 1:  wait x0, c -> item tower + item-id / class table gradients (set 0)
-    //   side 0:  wait c -> session-history encoder (set 2)
+  // ===== the tail of both four-stream schedules, behind [c] ([e]: an event is recorded).  Each encoder's slabs are reduced on its own
+  // stream (tags 3 / 4: they are large whatever the batch); its share of the SHARED intent-embedding slot stays untagged for the final flush
+  //   side 0:  session-history encoder (set 2, tag 3) -> flush 3 -> its intent_wgrad
+  //   main:    item-history encoder (set 1, tag 4) -> flush 4 -> its intent_wgrad -> [iid] -> join sides 0, 1, 2 -> final flush
+  //   table:   wait iid -> wait side 1     (the caller's table stream, intel_set_table_stream: the item-id table gradient is complete once the
+  //            item tower (side 1) and the item-history encoder (main stream, up to [iid]) are; see backward_entry for when the sweep really starts)
+  auto encoders_and_join = [&](Run& r) {
+    IntelCtx* c = r.ctx;
+    Run s0 = branch(r, 0, 2), e1 = branch(r, -1, 1);
+    redq_set_tag(c->rq, 3);
+    float* dE0 = encoder_branch(s0, 0);
+    if (!s0.rc) s0.ok(redq_flush_tag(c->rq, 3, s0.st));
+    redq_set_tag(c->rq, 0);
+    if (!s0.rc && dE0) intent_wgrad(s0, 0, dE0);
+    redq_set_tag(c->rq, 4);
+    float* dE1 = encoder_branch(e1, 1);
+    if (!e1.rc) e1.ok(redq_flush_tag(c->rq, 4, e1.st));
+    redq_set_tag(c->rq, 0);
+    if (!e1.rc && dE1) intent_wgrad(e1, 1, dE1);
+    r.ok(e1.rc); r.ok(s0.rc);
+    if (c->table_stream) {
+      r.ok((int)hipEventRecord(c->ev_x[3], r.st));
+      r.ok((int)hipStreamWaitEvent(c->table_stream, c->ev_x[3], 0));
+      if (c->table_stream != c->side[1]) wait_side(r, 1, c->table_stream);
+    }
+    join_streams(r, 3);
+    if (r.rc || !dE1 || !dE0) return;
+    RUN(redq_flush(c->rq, r.st));
+  };
+
+  // ===== the whole backward in one call (phase 0) on four streams, the session head as chain launches (chain.hip).  The d(intent) chain
+  // (head_bwd_b) is the critical link -- both encoders wait for it -- and it is a SMALL launch (B / 16 workgroups) that must not queue behind
+  // the towers' kernels for LDS.  Every branch reduces its own weight-gradient slabs on its own stream (tags 1 .. 5): the final flush (on the
+  // critical tail, in front of the dense groups' Adam) is left with the shared intent-embedding slot.
+  //   main:    head_bwd_a (above) -> pooling backward of the item tower (tag 2) -> [x0] -> wait x1 -> head_bwd_b -> [c] -> encoders_and_join
+  //   side 2:  wait fork -> pooling backward of the score tower (tag 1) -> [x1] -> score tower (set 3) -> flush 1 -> wait c -> the head's table
+  //            scatters (h_u's from dFEAT, context / user from dPREDIN) -> chain leaves, if leaves_behind_score
+  //   side 1:  wait x0 -> item tower + item-id / class table gradients (set 0) -> flush 2 -> chain leaves, if not leaves_behind_score
+  //   side 0:  wait c -> session-history encoder (encoders_and_join)
+  //   chain leaves (tag 5):  head_bwd_a_leaves -> wait c -> head_bwd_b_leaves -> flush 5
+  if (hfused) {
     IntelCtx* c = r.ctx;
     r.T = &y.tmp[0];
-    Run m = r;
-    Run s2 = branch(r, 2, 1), s1 = branch(r, 1, 0), s0 = branch(r, 0, 2);
-    // every branch reduces its own weight-gradient slabs on its own stream: the final flush (on the critical tail, in front of the dense
-    // groups' Adam) is left with the shared intent-embedding slot
-    defer = &lv_main;
+    Run s2 = branch(r, 2, 1), s1 = branch(r, 1, 0);
     r.ok((int)hipEventRecord(c->ev_fork, r.st));
     r.ok((int)hipStreamWaitEvent(c->side[2], c->ev_fork, 0));
     redq_set_tag(c->rq, 1);
-    pool_bwd_fused(s2, 1, y.dXS);                      // (its LayerNorm partials, when the tail is fused, belong to the score tower's tag)
+    pool_bwd(s2, 1, y.dXS);                            // (its LayerNorm partials, when the tail is fused, belong to the score tower's tag)
     r.ok((int)hipEventRecord(c->ev_x[1], s2.st));
     redq_set_tag(c->rq, 2);
-    pool_bwd_fused(m, 0, y.tmp[0].dXa);
-    r.ok(m.rc); r.ok(s2.rc);
+    pool_bwd(r, 0, y.tmp[0].dXa);
+    r.ok(s2.rc);
     if (r.rc) return;
     r.ok((int)hipEventRecord(c->ev_x[0], r.st));
     redq_set_tag(c->rq, 0);
@@ -2178,22 +2212,14 @@ void backward_impl(Run& r, const float* d_weights, const float* d_ens, const flo
     };
     {   // score tower: it needs its pooling backward only (the tower kernels leave room for the chain launches: tower32.hip)
       redq_set_tag(c->rq, 1);
-      Run t3 = s2;
-      t3.T = &y.tmp[3];
-      t3.rc = 0;
-      TowerBufs& w = y.tw[1];
-      float* dX0 = tower_bwd(t3, w, y.dXS, y.tmp[3].dXb, c->fused_tail[1]);
-      if (!t3.rc && dX0) wgrad(t3, dX0, w.d, bt.scores, K, M, w.d, K, INTEL_P_SCORE_W, INTEL_P_SCORE_B);
+      Run t3 = branch(r, 2, 3);
+      score_tower_bwd(t3);
       if (!t3.rc) t3.ok(redq_flush_tag(c->rq, 1, t3.st));
       // the head's leaves (nothing in this backward reads them): table scatters and the weight gradients of head_bwd_b's links
-      defer = nullptr;
       redq_set_tag(c->rq, 0);
       t3.ok((int)hipStreamWaitEvent(t3.st, c->ev_x[2], 0));
       if (!t3.rc) run_leaves(t3, lv_main, 0);
-      if (!t3.rc && r.G(INTEL_P_CTX_EMB))
-        t3.ok(launch_scatter_add_rows(y.dPREDIN, y.Pin, 0, D.d_c, bt.context_mh, B, r.G(INTEL_P_CTX_EMB), nullptr, 0, 0, t3.st));
-      if (!t3.rc && r.G(INTEL_P_UID_EMB))
-        t3.ok(launch_scatter_add_rows(y.dPREDIN, y.Pin, D.d_c, D.d_u, bt.u_id_c, B, r.G(INTEL_P_UID_EMB), nullptr, 0, 0, t3.st));
+      predin_scatters(t3);
       if (leaves_behind_score) chain_leaves(t3);
       r.ok(t3.rc);
     }
@@ -2204,62 +2230,40 @@ void backward_impl(Run& r, const float* d_weights, const float* d_ens, const flo
     if (!leaves_behind_score) chain_leaves(s1);
     r.ok(s1.rc);
     if (r.rc) return;
-    redq_set_tag(c->rq, 3);
-    float* dE0 = encoder_branch(s0, 0);
-    if (!s0.rc) s0.ok(redq_flush_tag(c->rq, 3, s0.st));      // (the encoders' slabs are large whatever the batch: always branch-local)
-    redq_set_tag(c->rq, 0);
-    if (!s0.rc && dE0) intent_wgrad(s0, 0, dE0);
-    Run e1 = r;
-    e1.T = &y.tmp[1];
-    e1.rc = 0;
-    redq_set_tag(c->rq, 4);
-    float* dE1 = encoder_branch(e1, 1);
-    if (!e1.rc) e1.ok(redq_flush_tag(c->rq, 4, e1.st));
-    redq_set_tag(c->rq, 0);
-    if (!e1.rc && dE1) intent_wgrad(e1, 1, dE1);
-    r.ok(e1.rc); r.ok(s0.rc);
-    if (c->table_stream) {
-      r.ok((int)hipEventRecord(c->ev_x[3], r.st));
-      r.ok((int)hipStreamWaitEvent(c->table_stream, c->ev_x[3], 0));
-      if (c->table_stream != c->side[1]) wait_side(r, 1, c->table_stream);
-    }
-    join_streams(r, 3);
-    if (r.rc || !dE1 || !dE0) return;
-    RUN(redq_flush(c->rq, r.st));
+    encoders_and_join(r);
     return;
   }
+  // ===== the whole backward in one call (phase 0) on four streams with the kernel-per-op head (head_fused_ok says no: cross_attention = 0,
+  // more than 1024 sessions, INTEL_HEAD_FUSED=0): nothing heavy waits for a chain of small launches it does not depend on.  Every branch
+  // reduces the slabs of ITS weights on its own stream when it is done (tags 1 .. 5) instead of leaving 0.5 GB of reduction to the tail.
+  //   main:    cross-attention backward of the item tower (tag 2) -> [x0] -> wait x1 -> d(intent) chain, d(pred_layer input) -> [c] -> encoders_and_join
+  //   side 2:  wait fork -> cross-attention backward of the score tower (tag 1) -> [x1] -> score tower (set 3) -> that cross attention's leaves
+  //            -> flush 1 -> wait c -> the head's and the item tower's cross-attention leaves + pred_layer weight gradient (tag 5) -> flush 5
+  //            -> context / user table scatters from dPREDIN
+  //   side 1:  wait x0 -> item tower + item-id / class table gradients (set 0) -> flush 2
+  //   side 0:  wait c -> session-history encoder (encoders_and_join)
   if (wide) {
     IntelCtx* c = r.ctx;
     r.T = &y.tmp[0];
-    Run m = r;                                   // main stream, set 0 for the B-row temporaries of the chain
-    Run s2 = branch(r, 2, 1), s1 = branch(r, 1, 0), s0 = branch(r, 0, 2);
+    Run s2 = branch(r, 2, 1), s1 = branch(r, 1, 0);
     r.ok((int)hipEventRecord(c->ev_fork, r.st));
     r.ok((int)hipStreamWaitEvent(c->side[2], c->ev_fork, 0));
-    // score tower (side 2): cross-attention backward, then its layers with set 3, then the pooling's weight gradients
-    // (every branch reduces the slabs of ITS weights on its own stream when it is done -- tags 1..4 -- instead of leaving
-    // 0.5 GB of reduction to the tail; the shared intent-embedding slot and the session head stay in the final flush)
-    defer = hfused ? &lv_main : &lv_score;      // (hfused: dQV is produced later, by head_bwd_b on the main stream -- every leaf goes behind it)
+    defer = &lv_score;      // the score tower's cross-attention leaves follow its layers on side 2; every other leaf (lv_main) goes behind [c]
     redq_set_tag(c->rq, 1);
-    if (hfused) pool_bwd_fused(s2, 1, y.dXS);
-    else xatt_bwd(s2, 1, y.dXS, y.tmp[1].dINT);
+    xatt_bwd(s2, 1, y.dXS, y.tmp[1].dINT);
     defer = &lv_main;
     r.ok((int)hipEventRecord(c->ev_x[1], s2.st));
     {
-      Run t3 = s2;
+      Run t3 = s2;          // (keeps the cross-attention backward's rc)
       t3.T = &y.tmp[3];
-      TowerBufs& w = y.tw[1];
-      float* dX0 = tower_bwd(t3, w, y.dXS, y.tmp[3].dXb, c->fused_tail[1]);
-      if (!t3.rc && dX0) wgrad(t3, dX0, w.d, bt.scores, K, M, w.d, K, INTEL_P_SCORE_W, INTEL_P_SCORE_B);
+      score_tower_bwd(t3);
       if (!t3.rc) run_leaves(t3, lv_score, 1);
       if (!t3.rc) t3.ok(redq_flush_tag(c->rq, 1, t3.st));
       r.ok(t3.rc);
     }
     redq_set_tag(c->rq, 2);
     r.ok(s2.rc);
-    // item tower: cross-attention backward on the main stream, layers on side 1
-    if (hfused) pool_bwd_fused(m, 0, y.tmp[0].dXa);
-    else xatt_bwd(m, 0, y.tmp[0].dXa, y.tmp[0].dINT);
-    r.ok(m.rc);
+    xatt_bwd(r, 0, y.tmp[0].dXa, y.tmp[0].dINT);
     if (r.rc) return;
     r.ok((int)hipEventRecord(c->ev_x[0], r.st));
     r.ok((int)hipStreamWaitEvent(c->side[1], c->ev_x[0], 0));
@@ -2267,68 +2271,42 @@ void backward_impl(Run& r, const float* d_weights, const float* d_ens, const flo
     if (!s1.rc) s1.ok(redq_flush_tag(c->rq, 2, s1.st));
     r.ok(s1.rc);
     redq_set_tag(c->rq, 0);
-    // d(intent) chain (needs both cross-attention backwards)
-    r.ok((int)hipStreamWaitEvent(r.st, c->ev_x[1], 0));
-    if (hfused) {
-      head_bwd_b(r, d_intents);      // dQV of both towers, d(intent) summed, softmax backward, d(pred_layer input)
-    } else {
-      RUN(launch_add2(y.dINTENT, y.tmp[0].dINT, (long long)B * I, y.dINTENT, r.st));
-      RUN(launch_add2(y.dINTENT, y.tmp[1].dINT, (long long)B * I, y.dINTENT, r.st));
-      if (d_intents) RUN(launch_add2(y.dINTENT, d_intents, (long long)B * I, y.dINTENT, r.st));
-      RUN(launch_softmax_rows_bwd(y.INTENTS, y.dINTENT, B, I, y.dLOGITS, r.st));
-      lin(r, y.dLOGITS, I, B, I, y.pPredT, y.Pin, y.dPREDIN, y.Pin, e0);
-    }
+    r.ok((int)hipStreamWaitEvent(r.st, c->ev_x[1], 0));      // d(intent) needs both cross-attention backwards
+    dintent_chain(r, d_intents);
     if (r.rc) return;
-    // the two encoders need the chain's d(pred_layer input): session history on side 0 (set 2), item history on the main
-    // stream (set 1).  The leaves of the session head go to side 2 behind the score tower (the shortest branch): off the
-    // critical chain, and in the same host order as before (ahead of the encoders' shares of the shared intent-embedding slot).
+    lin(r, y.dLOGITS, I, B, I, y.pPredT, y.Pin, y.dPREDIN, y.Pin, e0);
+    if (r.rc) return;
+    // The leaves of the session head go to side 2 behind the score tower (the shortest branch): off the critical chain, and ahead (in host
+    // order) of the encoders' shares of the shared intent-embedding slot.
     r.ok((int)hipEventRecord(c->ev_x[2], r.st));
     r.ok((int)hipStreamWaitEvent(c->side[0], c->ev_x[2], 0));
     r.ok((int)hipStreamWaitEvent(c->side[2], c->ev_x[2], 0));
-    defer = nullptr;
     {
-      Run lf = s2;
-      lf.rc = 0;
+      Run lf = branch(r, 2, 1);
       // the leaves' own slots (fusion weights, pooling projections, pred_layer) are reduced right here (tag 5); the
       // intent-embedding slot, shared with the encoders, stays untagged for the final flush
       run_leaves(lf, lv_main, 5);
-      if (!hfused) wgrad(lf, y.dLOGITS, I, y.PREDIN, y.Pin, B, I, y.Pin, INTEL_P_PRED_W, INTEL_P_PRED_B);
+      wgrad(lf, y.dLOGITS, I, y.PREDIN, y.Pin, B, I, y.Pin, INTEL_P_PRED_W, INTEL_P_PRED_B);
       if (!lf.rc) lf.ok(redq_flush_tag(c->rq, 5, lf.st));
       redq_set_tag(c->rq, 0);
-      if (!lf.rc && r.G(INTEL_P_CTX_EMB))
-        lf.ok(launch_scatter_add_rows(y.dPREDIN, y.Pin, 0, D.d_c, bt.context_mh, B, r.G(INTEL_P_CTX_EMB), nullptr, 0, 0, lf.st));
-      if (!lf.rc && r.G(INTEL_P_UID_EMB))
-        lf.ok(launch_scatter_add_rows(y.dPREDIN, y.Pin, D.d_c, D.d_u, bt.u_id_c, B, r.G(INTEL_P_UID_EMB), nullptr, 0, 0, lf.st));
+      predin_scatters(lf);
       r.ok(lf.rc);
     }
     if (r.rc) return;
-    redq_set_tag(c->rq, 3);
-    float* dE0 = encoder_branch(s0, 0);
-    if (!s0.rc) s0.ok(redq_flush_tag(c->rq, 3, s0.st));
-    redq_set_tag(c->rq, 0);
-    if (!s0.rc && dE0) intent_wgrad(s0, 0, dE0);
-    Run e1 = r;
-    e1.T = &y.tmp[1];
-    e1.rc = 0;
-    redq_set_tag(c->rq, 4);
-    float* dE1 = encoder_branch(e1, 1);
-    if (!e1.rc) e1.ok(redq_flush_tag(c->rq, 4, e1.st));
-    redq_set_tag(c->rq, 0);
-    if (!e1.rc && dE1) intent_wgrad(e1, 1, dE1);
-    r.ok(e1.rc); r.ok(s0.rc);
-    if (c->table_stream) {
-      // the item-id table gradient is complete once the item tower (side 1) and the item-history encoder (main stream, up to
-      // here) are: the caller's optimizer sweep of the table may start without waiting for the other two branches
-      r.ok((int)hipEventRecord(c->ev_x[3], r.st));
-      r.ok((int)hipStreamWaitEvent(c->table_stream, c->ev_x[3], 0));
-      if (c->table_stream != c->side[1]) wait_side(r, 1, c->table_stream);
-    }
-    join_streams(r, 3);
-    if (r.rc || !dE1 || !dE0) return;
-    RUN(redq_flush(c->rq, r.st));
+    encoders_and_join(r);
     return;
   }
-  constexpr bool enc0_early = true;      // the session-history encoder joins phase 1 on a third stream
+  // ===== the two-call form (phase 1, then phase 2: the caller overlaps the item-id table's all-reduce with phase 2) and the one-stream
+  // form (phase 0 with concurrency off -- INTEL_STREAMS=0, intel_set_concurrency(ctx, 0): fork / join / branch leave everything on the
+  // caller's stream, in this host order).  No leaf is deferred: each runs where it is met.
+  //   phase 1
+  //   main:    [fork] -> cross-attention backward of the item tower -> join side 0 -> d(intent) chain, pred_layer weight gradient, d(pred_layer input),
+  //            its table scatters -> [fork] -> item tower + item-id / class table gradients (set 0) -> join sides 0, 1 -> intent_wgrad of
+  //            encoder 1, then 0 -> flush
+  //   side 0:  wait fork -> cross-attention backward of the score tower (dXS stays parked for phase 2) ... wait fork -> item-history encoder (set 1)
+  //   side 1:  wait fork -> session-history encoder (set 2)
+  //   phase 2
+  //   main:    score tower (set 0) -> flush
   if (phase != 2) {
     // cross-attention backward of both towers first: d(intent) is then complete and the intent path can
     // start while the (heavy) tower layers are still running
@@ -2342,57 +2320,34 @@ void backward_impl(Run& r, const float* d_weights, const float* d_ens, const flo
     }
     join_streams(r, 1);
     if (r.rc) return;
-    RUN(launch_add2(y.dINTENT, y.tmp[0].dINT, (long long)B * I, y.dINTENT, r.st));
-    RUN(launch_add2(y.dINTENT, y.tmp[1].dINT, (long long)B * I, y.dINTENT, r.st));
-    if (d_intents) RUN(launch_add2(y.dINTENT, d_intents, (long long)B * I, y.dINTENT, r.st));
-    RUN(launch_softmax_rows_bwd(y.INTENTS, y.dINTENT, B, I, y.dLOGITS, r.st));
+    dintent_chain(r, d_intents);
+    if (r.rc) return;
     wgrad(r, y.dLOGITS, I, y.PREDIN, y.Pin, B, I, y.Pin, INTEL_P_PRED_W, INTEL_P_PRED_B);
     lin(r, y.dLOGITS, I, B, I, y.pPredT, y.Pin, y.dPREDIN, y.Pin, e0);
+    predin_scatters(r);
     if (r.rc) return;
-    if (r.G(INTEL_P_CTX_EMB))
-      RUN(launch_scatter_add_rows(y.dPREDIN, y.Pin, 0, D.d_c, bt.context_mh, B, r.G(INTEL_P_CTX_EMB), nullptr, 0, 0, r.st));
-    if (r.G(INTEL_P_UID_EMB))
-      RUN(launch_scatter_add_rows(y.dPREDIN, y.Pin, D.d_c, D.d_u, bt.u_id_c, B, r.G(INTEL_P_UID_EMB), nullptr, 0, 0, r.st));
-    // phase 1 branches: item tower layers (main, set 0) || item-history encoder (side 0, set 1): after the
-    // join the item-id table gradient is complete
-    // Both encoders' backward chains are long runs of small launches (B*H rows): the session-history encoder joins phase 1 on a
-    // third stream (set 2) instead of trailing the score tower in phase 2, where it was the critical path.
+    // after the join the item-id table gradient is complete.  Both encoders' backward chains are long runs of small launches (B*H rows): the
+    // session-history encoder joins phase 1 on a third stream instead of trailing the score tower in phase 2, where it was the critical path.
     float *dE1 = nullptr, *dE0 = nullptr;
-    fork_streams(r, enc0_early ? 2 : 1);
+    fork_streams(r, 2);
     {
       Run b0 = branch(r, -1, 0), b1 = branch(r, 0, 1), b2 = branch(r, 1, 2);
       item_tower_bwd(b0, y.tmp[0].dXa);
       dE1 = encoder_branch(b1, 1);
-      if (enc0_early) dE0 = encoder_branch(b2, 0);
+      dE0 = encoder_branch(b2, 0);
       r.ok(b0.rc); r.ok(b1.rc); r.ok(b2.rc);
     }
-    join_streams(r, enc0_early ? 2 : 1);
-    if (r.rc || !dE1 || (enc0_early && !dE0)) return;
-    r.T = &y.tmp[0];
+    join_streams(r, 2);
+    if (r.rc || !dE1 || !dE0) return;
     intent_wgrad(r, 1, dE1);
-    if (enc0_early) intent_wgrad(r, 0, dE0);
+    intent_wgrad(r, 0, dE0);
     if (r.rc) return;
     RUN(redq_flush(r.ctx->rq, r.st));
   }
   if (phase != 1) {
-    // phase 2: score tower layers (main, set 0)
-    float* dE0 = nullptr;
-    if (!enc0_early) fork_streams(r, 1);
-    {
-      Run b0 = branch(r, -1, 0), b1 = branch(r, 0, 1);
-      // the score tower's output gradient was parked in dXS by phase 1; tower_bwd ping-pongs dXS <-> dXb
-      {
-        TowerBufs& w = y.tw[1];
-        float* dX0 = tower_bwd(b0, w, y.dXS, y.tmp[0].dXb, r.ctx->fused_tail[1]);
-        if (!b0.rc && dX0) wgrad(b0, dX0, w.d, bt.scores, K, M, w.d, K, INTEL_P_SCORE_W, INTEL_P_SCORE_B);
-      }
-      if (!enc0_early) dE0 = encoder_branch(b1, 0);
-      r.ok(b0.rc); r.ok(b1.rc);
-    }
-    if (!enc0_early) join_streams(r, 1);
-    if (r.rc || (!enc0_early && !dE0)) return;
-    r.T = &y.tmp[0];
-    if (!enc0_early) intent_wgrad(r, 0, dE0);
+    Run b0 = branch(r, -1, 0);      // the score tower's output gradient was parked in dXS by phase 1
+    score_tower_bwd(b0);
+    r.ok(b0.rc);
     if (r.rc) return;
     RUN(redq_flush(r.ctx->rq, r.st));
   }
