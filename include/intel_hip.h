@@ -402,6 +402,31 @@ int intel_era_fitness(int P, int B, int L, int F, int n_hidden, const int* hidde
                       const int* ranking, const int* session_len, int width, double* gain_sum, float* pred_out, void* workspace,
                       void* stream);
 
+/* ---- aWELv baseline (per-user fusion weights) ------------------------------------------------------
+ * The comparison method of models/supervise/aWELv.py (Liu, Du, Wu, JMLR 23 (2022)), the model aWELv_IntEL extends: a user
+ * embedding table E [users, H] and a base-ranker embedding table M [K, H].  All tensors fp32 unless noted; u_id [B] int32. */
+/* aWELv.forward (aWELv.py:26-40): z[b,k] = sum_h E[u_b,h] M[k,h] (:31-35); w[b,:] = softmax(z[b,:]) with the row maximum
+ * subtracted (:36); weights[b,l,:] = w[b,:] and ens_score[b,l] = sum_k w[b,k] scores[b,l,k] for EVERY l < L (:36-37: the
+ * reference repeats over the whole padded list and does not mask).  w [B,K] is kept for the backward.  A session whose id is
+ * outside [0, users) is treated as a zero embedding; the table is never indexed outside.
+ * Limits (INTEL_E_ARG otherwise): 1 <= K <= 16, H % 4 == 0, 4 <= H <= 256, L >= 1, B >= 1; tables 16-byte aligned. */
+int intel_awelv_forward(int B, int L, int K, int H, const float* uid_table, long long users, const float* model_table,
+                        const int* u_id, const float* scores /*[B,L,K]*/, float* w /*[B,K]*/, float* weights /*[B,L,K]*/,
+                        float* ens_score /*[B,L]*/, void* stream);
+/* What autograd returns for aWELv.py:31-37: gw[b,k] = sum_{l<L} (d_ens[b,l] scores[b,l,k] + d_weights[b,l,k]);
+ * dz[b,k] = w_k sum_j w_j (gw_k - gw_j) (the softmax backward of :36 in its pairwise form: no cancellation when the softmax
+ * saturates); d_uid_table[u_b,:] += sum_k dz[b,k] M[k,:] (the nn.Embedding backward of :31; float atomics, a user may occur
+ * several times; ADDED into, the caller zeroes it) and row_flags[u_b] = 1 when given (see intel_adam_step_rows);
+ * d_model_table[k,:] = sum_b dz[b,k] E[u_b,:] (:34; WRITTEN, bit-reproducible: per-workgroup partials in `workspace`,
+ * intel_awelv_backward_workspace_bytes bytes -- bounded in B --, then a fixed-order pass).  d_weights may be NULL (= zeros).
+ * A session whose id is outside [0, users) receives no gradient.  Limits as intel_awelv_forward. */
+size_t intel_awelv_backward_workspace_bytes(int B, int K, int H);
+int intel_awelv_backward(int B, int L, int K, int H, const float* uid_table, long long users, const float* model_table,
+                         const int* u_id, const float* scores, const float* w, const float* d_ens /*[B,L]*/,
+                         const float* d_weights /*[B,L,K] or NULL*/, float* d_uid_table /*[users,H], ADDED into*/,
+                         unsigned char* row_flags /*[users] or NULL*/, float* d_model_table /*[K,H], WRITTEN*/,
+                         void* workspace, void* stream);
+
 /* ---- input feed ------------------------------------------------------------------------------ */
 /* Device-side batch assembly: the work of the reference's per-sample Dataset._get_feed_dict chain
  * (models/BaseModel.py:158-197, models/GeneralSeq.py:35-54, models/IntEL/IntEL.py:220-239) and of

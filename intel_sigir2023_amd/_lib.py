@@ -144,6 +144,8 @@ EXPORTS = [
     'intel_op_gru_workspace_bytes', 'intel_op_gru_fwd', 'intel_op_gru_bwd',
     # ERA baseline (era.py)
     'intel_era_features', 'intel_era_fitness_workspace_bytes', 'intel_era_fitness',
+    # aWELv baseline (awelv.py)
+    'intel_awelv_forward', 'intel_awelv_backward_workspace_bytes', 'intel_awelv_backward',
 ]
 
 
@@ -227,6 +229,9 @@ def _declare(l):
     sig('intel_era_features', i, [i, i, i, vp, vp, i, vp, vp])
     sig('intel_era_fitness_workspace_bytes', sz, [i, i])
     sig('intel_era_fitness', i, [i, i, i, i, i, C.POINTER(C.c_int), vp, vp, vp, vp, i, vp, vp, vp, vp])
+    sig('intel_awelv_forward', i, [i, i, i, i, vp, ll, vp, vp, vp, vp, vp, vp, vp])
+    sig('intel_awelv_backward_workspace_bytes', sz, [i, i, i])
+    sig('intel_awelv_backward', i, [i, i, i, i, vp, ll, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp])
     sig('intel_rows_take', i, [vp, i, vp, i, vp, i, vp])
     sig('intel_rows_add', i, [vp, i, vp, i, vp, vp])
     sig('intel_rows_compact', i, [vp, C.c_longlong, vp, i, vp, vp])

@@ -20,11 +20,12 @@ from . import data as data_mod
 from . import feed
 from . import parallel
 from . import synth
+from .awelv import aWELv, plain_loss_message
 from .era import ERA, ERARunner
 from .model import IntEL, aWELv_IntEL
 from .runner import BaseRunner
 
-MODELS = {'IntEL': IntEL, 'aWELv_IntEL': aWELv_IntEL, 'ERA': ERA}
+MODELS = {'IntEL': IntEL, 'aWELv_IntEL': aWELv_IntEL, 'ERA': ERA, 'aWELv': aWELv}
 LOSSES = {n: getattr(loss_mod, n) for n in ('BPRloss', 'Listloss', 'MSEloss', 'IntBPRloss', 'IntListloss', 'IntMSEloss')}
 RUNNERS = {'BaseRunner': BaseRunner, 'ERARunner': ERARunner}
 
@@ -88,6 +89,8 @@ def build_parser(argv=None):
     for name, table in ((init_args.model_name, MODELS), (init_args.loss_name, LOSSES), (init_args.runner_name, RUNNERS)):
         if name not in table:
             raise SystemExit('unknown class %s (available: %s)' % (name, ', '.join(table)))
+    if init_args.model_name == 'aWELv' and init_args.loss_name.startswith('Int'):
+        raise SystemExit(plain_loss_message(init_args.loss_name))
     parser = argparse.ArgumentParser(description='IntEL on MI355X')
     parse_global_args(parser)
     MODELS[init_args.model_name].parse_model_args(parser)

@@ -251,6 +251,8 @@ class BaseRunner(object):
         model.train()
         losses = []
         if self.use_engine:
+            if self.engine is None and getattr(model, 'ENGINE', IntELEngine) is not IntELEngine:      # a model with a fused step of its own (awelv.py)
+                self.engine = model.ENGINE(model, loss_name or type(criterion).__name__, self.args, lr=self.learning_rate, l2=self.l2)
             if self.engine is None:
                 # lazy table Adam (engine.py): evaluation catches its batches' rows up inside the forward pass, state_dict()
                 # (save_model) and load_state_dict() settle the whole table through the engine's hooks
@@ -298,8 +300,9 @@ class BaseRunner(object):
             preds.extend(sel(out['ens_score'].cpu().numpy()))
             ranks.extend(sel(batch['ranking'].cpu().numpy()))
             slens.extend(sel(batch['session_len'].cpu().numpy().tolist()))
-            true_int.extend(sel(batch['intents'].cpu().numpy()))
-            pred_int.extend(sel(out['intents'].cpu().numpy()))
+            if 'intents' in out:                      # a model without an intent prediction (aWELv): no intent metrics, like the reference
+                true_int.extend(sel(batch['intents'].cpu().numpy()))
+                pred_int.extend(sel(out['intents'].cpu().numpy()))
         if parallel.world_size() > 1:
             # data parallel: every rank evaluated its shard of each batch; the metrics are means over ALL sessions, so the
             # per-session records are gathered (rank order = session order) and every rank computes the same numbers
@@ -358,8 +361,9 @@ class BaseRunner(object):
             counts[3] += ew.sum()
             nsess.append(ew.sum().reshape(()))
             keep = ew > 0
-            true_int.append(batch['intents'][keep])
-            pred_int.append(out['intents'][keep])
+            if 'intents' in out:                      # a model without an intent prediction (aWELv): no intent metrics, like the reference
+                true_int.append(batch['intents'][keep])
+                pred_int.append(out['intents'][keep])
         lossv = torch.stack(losses)
         if parallel.world_size() > 1:
             parallel.allreduce_sum_([sums, counts])
@@ -371,8 +375,8 @@ class BaseRunner(object):
         res = dict()
         if self.test_ensemble:
             res.update(self.reduce_device_metrics(sums.cpu().numpy(), counts.cpu().numpy()[:3], float(counts[3]), topk, metrics))
-        ti = torch.cat(true_int).cpu().numpy()
-        pi = torch.cat(pred_int).cpu().numpy()
+        ti = torch.cat(true_int).cpu().numpy() if true_int else np.zeros((0, 0))
+        pi = torch.cat(pred_int).cpu().numpy() if pred_int else np.zeros((0, 0))
         if parallel.world_size() > 1:
             parts = parallel.allgather_object((ti, pi))
             ti, pi = np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
